@@ -16,7 +16,17 @@ GPUs (strong scaling: the frame is fixed, its 32x32 tiles are dealt tile % N):
     (a host thread and stream per GPU, xGMI peer copies to GPU 0).
   Both forms do the gather inside the timed step.
 
-The JSON line also carries
+A plain run sets up, warms up, times the `--steps` frames and prints the JSON line;
+`--dump-outputs DIR` also writes what the last timed step returned (DIR/canvas.npy, the
+float64 (H, W, 4) canvas: the scene, the seed and the per-sample RNG streams are fixed, so
+two runs with the same arguments render the same frame). Everything below takes runs of its
+own and is measured only with `--full` (single GPU); a plain run leaves it `null`.
+
+With `--full` the JSON line also carries
+  detail:       host_canvas, accumulation_check and reference_tree: the same frame with the
+                canvas returned to host memory, through the bitwise recursion, and on izpi's
+                own tree, in the same process (the forward form and the GPU-built tree only
+                count if their image is the recursion's and the reference tree's).
   roofline:     the dominant kernel k_trace2 against HBM peak. `achieved` = L2 memory-side
                 traffic per frame, measured by rocprofv3 PMC passes (FETCH_SIZE x2 +
                 WRITE_SIZE; the x2 is MI355X_MICROARCH.md's gfx950 correction, checked for
@@ -69,23 +79,30 @@ def parse(argv=None):
     p.add_argument("--warmup", type=int, default=2)
     p.add_argument("--config", default="C3")
     p.add_argument("--spp", type=int, default=None, help="override spp (debug only; the metric uses 512)")
-    p.add_argument("--cpu-seconds", type=float, default=20.0, help="budget of the CPU-baseline sample")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 PMC passes (roofline traffic)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run, at N=1, the same-run checks (host canvas, recursion, "
+                        "reference tree), the rocprofv3 PMC passes and the CPU baseline; a plain run only sets up, "
+                        "warms up, times the steps and prints the result line")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write what the last timed step returned to DIR/<name>.npy (canvas.npy: the float64 "
+                        "(H, W, 4) canvas)")
+    p.add_argument("--cpu-seconds", type=float, default=20.0, help="budget of the CPU-baseline sample (--full)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="leave the CPU baseline out of --full")
+    p.add_argument("--no-pmc", action="store_true", help="leave the rocprofv3 PMC passes (roofline traffic) out of --full")
     p.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     p.add_argument("--dry-run", action="store_true",
                    help="launcher plumbing only (rank setup, tile shares, barriers, max of times): no GPU work")
     p.add_argument("--scene", default=None, help="render a transport.Scene file (.pbtxt/.izpi) at the config's size")
     p.add_argument("--bvh", default="gpu", choices=["reference", "gpu"],
-                   help="gpu (default): the GPU linear BVH4 builder, checked at N=1 against a frame on the "
+                   help="gpu (default): the GPU linear BVH4 builder, checked by --full at N=1 against a frame on the "
                         "reference tree; reference: hitable.NewBVH4's tree rebuilt bit for bit on the host")
     p.add_argument("--bvh-leaf-max", type=int, default=None, help="primitives per leaf of the GPU-built tree")
     p.add_argument("--no-reference-check", action="store_true",
-                   help="skip the reference-tree frame (timing and image comparison) of --bvh gpu")
+                   help="leave the same-run checks (host canvas, recursion, reference-tree frame) out of --full")
     p.add_argument("--obj", default=None, help="C3 with this OBJ mesh (e.g. the Stanford dragon) instead of the "
                                                "synthetic one")
     p.add_argument("--accumulation", default="forward", choices=["forward", "recursive"],
-                   help="forward (default): IZPI_ACC_FORWARD, checked at N=1 against frames of the bitwise "
+                   help="forward (default): IZPI_ACC_FORWARD, checked by --full at N=1 against frames of the bitwise "
                         "recursion in the same run (pixel RMSE < 1e-6, same NaN / Inf pixels, else the recursion's "
                         "figures are reported); recursive: IZPI_ACC_RECURSIVE, bit-identical to the oracle")
     return p.parse_args(argv)
@@ -140,6 +157,32 @@ STAT_KEYS = ("node_visits", "tri_tests", "sph_tests", "light_tri_tests", "light_
 def add_stats(agg, st):
     for k in STAT_KEYS:
         agg[k] += float(st[k]) if st else 0.0
+
+
+# ---------------------------------------------------------------- --dump-outputs
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(out_dir, arrays, max_bytes=DUMP_MAX_BYTES):
+    """Write each of `arrays` ({name: ndarray}) as out_dir/<name>.npy, float32 kept, anything
+    else as float64. All files together hold at most `max_bytes` of data: an array over its
+    equal share of that is written as a fixed sample of its flattened elements (seeded, in
+    index order, the same for every run of that shape). Returns {name: elements written}."""
+    import numpy as np
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    share = max_bytes // max(len(arrays), 1)
+    written = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = np.ascontiguousarray(a, np.float32 if a.dtype == np.float32 else np.float64)
+        keep = share // a.itemsize
+        if a.size > keep:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(out_dir / (name + ".npy"), a)
+        written[name] = int(a.size)
+    return written
 
 
 # ---------------------------------------------------------------- PMC passes
@@ -472,9 +515,16 @@ def main():
         print(json.dumps({"pmc_child": True, "ms": elapsed * 1e3}), flush=True)
         return
 
-    want_checks = mode == "single" and not args.no_reference_check
+    # --full (single GPU): the checks and measurements that take frames or processes of their own
+    full = args.full and mode == "single"
+    want_checks = full and not args.no_reference_check
     elapsed, agg, img, info = timed(args.bvh, args.steps, args.warmup, keep=want_checks)
     kept = info.pop("renderer", None)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the canvas of the last timed step (--gpus N in one process times frames that stay on
+        # device 0: there it is the one further frame rendered to the host, the same request)
+        dumped = dump_outputs(args.dump_outputs, {"canvas": img})
     samples_per_step = cfg.width * cfg.height * spp
     value = samples_per_step * args.steps / elapsed / 1e6
     ref_check = acc_check = host_check = None
@@ -550,7 +600,7 @@ def main():
     if rank != 0:
         dist.destroy_process_group()
         return
-    pmc = traffic_summary(pmc_children(args)) if (mode == "single" and not args.no_pmc) else {}
+    pmc = traffic_summary(pmc_children(args)) if (full and not args.no_pmc) else {}
     roof = {"bound": "hbm", "kernel": "k_trace2", "peak": HBM_PEAK_GBS, "unit": "GB/s",
             "achieved": None, "frac": None, "traffic": None,
             "achieved_algorithmic": round(achieved_alg, 2),
@@ -598,7 +648,7 @@ def main():
     elif pmc.get("error"):
         roof["pmc_error"] = pmc["error"]
     cpu = None
-    if mode == "single" and not args.no_cpu_baseline:
+    if full and not args.no_cpu_baseline:
         cpu = cpu_baseline(cfg, scene, args.cpu_seconds, spp, args.bvh, info.get("leaf_max"))
         # like for like: the GPU and the CPU oracle on the same tree
         cpu["gpu_speedup"] = value / cpu["value"]
@@ -613,6 +663,7 @@ def main():
         "n_gpus": n_gpus,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": full,
         "ms_per_step": round(elapsed / args.steps * 1e3, 3),
         # a fresh renderer's first frame, workspace allocation included: what izpi's leader
         # sees, which renders one frame per process (leader.go:155-158, renderer.go:170,213)
@@ -661,6 +712,7 @@ def main():
             "accumulation_check": acc_check,
             "host_canvas": host_check,
             "image_mean_rgb": [float(x) for x in img[1:, :, :3].mean(axis=(0, 1))] if img is not None else None,
+            "dumped_outputs": dumped,
         },
     }
     print(json.dumps(line), flush=True)
