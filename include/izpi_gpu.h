@@ -281,8 +281,9 @@ int izpi_gpu_build_bvh4(izpi_ctx* ctx, const double* boxes, uint32_t n, uint32_t
  * Render fans out over the GPUs of the node in ONE call, as RendererImpl.Render fans
  * out over its workers (render/renderer.go:123-147): one host thread and stream per
  * device instead of one goroutine per core. The frame's tiles (common.Tiles in
- * grid.WalkGrid's spiral order, or req->tiles) are dealt tile % G == i; device i renders
- * its share packed; the shares are gathered to device 0 (peer copies over xGMI), which
+ * grid.WalkGrid's spiral order, or req->tiles) become the units of izpi_host_share_units
+ * (quarter tiles, where they can be cut), dealt unit % G == i (izpi_host.h lists the
+ * steps); device i renders its share packed; the shares are gathered to device 0 (peer copies over xGMI), which
  * scatters them into the W*H*4 canvas (row H - y, rgb.go:41) and applies req->post.
  * Per pixel-sample RNG streams make the canvas bit-identical for every G. A device may
  * appear twice in `devices` (two contexts on one GPU). */

@@ -86,9 +86,26 @@ const char* izpi_host_last_error(void);
  * (grid/grid.go:27-130): writes up to max_tiles entries of x0,y0,x1,y1; returns count. */
 uint32_t izpi_host_tiles(uint32_t width, uint32_t height, uint32_t* tiles, uint32_t max_tiles);
 
-/* Multi-GPU share of a tile list (the rule izpi_gpu_multi_render / izpi_gpu_render_rank
- * use): copies tiles t with t % num_shares == share, in order, into `out`; returns how
- * many. The largest share has ceil(num_tiles / num_shares) tiles. */
+/* How izpi_gpu_multi_render / izpi_gpu_render_rank split a frame over num_shares devices,
+ * step by step (the device path is exactly these five):
+ *   1. izpi_host_share_units: the frame's tiles -> the units that are dealt;
+ *   2. izpi_host_share_tiles: the units of share r (unit % num_shares == r);
+ *   3. izpi_host_share_block: the padded size of every share's packed block;
+ *   4. each share is rendered packed (IZPI_OUT_PACKED) into its block;
+ *   5. izpi_host_assemble_shares (on the device: k_unpack) scatters the gathered blocks
+ *      into the canvas.
+ * Steps 2, 3 and 5 take the unit list of step 1 as their `tiles`. */
+
+/* The units a frame's tiles are dealt in when it is split into num_shares shares: with
+ * num_shares > 1 and tiles that are equal-sized, even in both extents and at least
+ * 16 x 16, every tile becomes its four quarters (in the tile's order, then rows j, then
+ * columns i); otherwise the list is copied unchanged. `out` holds [4 * num_tiles][4];
+ * returns the number of units. */
+uint32_t izpi_host_share_units(const uint32_t* tiles, uint32_t num_tiles, uint32_t num_shares, uint32_t* out);
+
+/* One share of a list of units (izpi_host_share_units; any tile list deals the same way):
+ * copies units t with t % num_shares == share, in order, into `out`; returns how many.
+ * The largest share has ceil(num_tiles / num_shares) of them. */
 uint32_t izpi_host_share_tiles(const uint32_t* tiles, uint32_t num_tiles, uint32_t share, uint32_t num_shares,
                                uint32_t* out);
 
@@ -97,16 +114,19 @@ uint32_t izpi_host_share_tiles(const uint32_t* tiles, uint32_t num_tiles, uint32
  * 32 spp: -2.9% per frame with 2). The Python host, the C replay and the Go shim all use it. */
 uint32_t izpi_host_bvh_leaf_max(const izpi_scene_desc* desc);
 
-/* Doubles per padded share block of a packed multi-GPU gather: ceil(num_tiles /
+/* Doubles per padded share block of a packed multi-GPU gather, over the units
+ * (izpi_host_share_units: num_tiles of them, tile_w x tile_h each): ceil(num_tiles /
  * num_shares) * tile_w * tile_h * 4 (every share's block has this size). */
 uint64_t izpi_host_share_block(uint32_t num_tiles, uint32_t tile_w, uint32_t tile_h, uint32_t num_shares);
 
 /* What the root of izpi_gpu_multi_render / izpi_gpu_render_rank does after the gather,
- * on the host: block r of `gathered` (izpi_host_share_block doubles each) holds share r's
- * tiles packed (IZPI_OUT_PACKED); every pixel is scattered to canvas row height - y
- * (render/rgb.go:41; sample row y = 0 has no canvas row). The same index rule as the
- * device's k_unpack. Replaces the framebuffer assembly of renderer.go:172-211 (workers
- * write their tiles into the shared canvas). Tiles must be equal-sized and in bounds. */
+ * on the host, with `tiles` the units those deal (izpi_host_share_units): block r of
+ * `gathered` (izpi_host_share_block doubles each) holds share r's units
+ * (izpi_host_share_tiles) packed (IZPI_OUT_PACKED); every pixel is scattered to canvas
+ * row height - y (render/rgb.go:41; sample row y = 0 has no canvas row). The same index
+ * rule as the device's k_unpack. Replaces the framebuffer assembly of renderer.go:172-211
+ * (workers write their tiles into the shared canvas). Units must be equal-sized and in
+ * bounds. */
 int izpi_host_assemble_shares(uint32_t width, uint32_t height, const uint32_t* tiles, uint32_t num_tiles,
                               uint32_t num_shares, const double* gathered, double* canvas);
 

@@ -747,14 +747,16 @@ int render_body(izpi_ctx* ctx, const izpi_render_req* req, double* out_dev) {
 }
 
 // ------------------------------------------------------------------ multi-GPU
-// The frame is split into G shares: tile t (in common.Tiles' spiral order, each cut into
-// quarters: make_shares) goes to share t % G, so the costly centre tiles spread over all
-// devices. Share r is rendered packed
-// (IZPI_OUT_PACKED) into d_share, padded to the largest share's size so that one gather
-// moves equal blocks; the root scatters share r's tiles from block r into the canvas.
+// The frame is split into G shares: its tiles (common.Tiles' spiral order) become the units
+// of izpi_host_share_units (quarter tiles, where they can be cut) and unit u goes to share
+// u % G (izpi_host_share_tiles), so the costly centre tiles spread over all devices. Share
+// r is rendered packed (IZPI_OUT_PACKED) into d_share, padded to the largest share's size
+// (izpi_host_share_block) so that one gather moves equal blocks; the root scatters share
+// r's units from block r into the canvas (k_unpack; on the host izpi_host_assemble_shares).
 struct Shares {
-  std::vector<uint32_t> all;  // the frame's tiles, [n][4]
+  std::vector<uint32_t> all;  // the units the frame is dealt in, [n][4]
   uint32_t n = 1;             // shares
+  uint32_t tw = 0, th = 0;    // a unit's extent
   size_t block = 0;           // doubles per (padded) share
   std::vector<uint32_t> mine(uint32_t r) const {
     std::vector<uint32_t> t(all.size());
@@ -768,51 +770,45 @@ size_t share_block(size_t ntiles, uint32_t tw, uint32_t th, uint32_t n) { return
 int make_shares(izpi_ctx* ctx, const izpi_render_req* req, uint32_t n, Shares& sh) {
   if (!req || req->width == 0 || req->height == 0) { ctx->err = "invalid render request"; return IZPI_ERR_INVALID; }
   if (req->out_layout != IZPI_OUT_CANVAS) { ctx->err = "multi-GPU renders produce a canvas (IZPI_OUT_CANVAS)"; return IZPI_ERR_INVALID; }
-  int rc = request_tiles(ctx, req, sh.all);
+  std::vector<uint32_t> tiles;
+  int rc = request_tiles(ctx, req, tiles);
   if (rc) return rc;
-  uint32_t tw = 0, th = 0;
-  if (!validate_tiles(req, sh.all.data(), (uint32_t)(sh.all.size() / 4), &tw, &th)) {
+  sh.all.resize(4 * tiles.size());
+  sh.all.resize(4 * (size_t)izpi_host_share_units(tiles.data(), (uint32_t)(tiles.size() / 4), n, sh.all.data()));
+  // (the units cover exactly the tiles' pixels: they are valid where the request's tiles are)
+  if (!validate_tiles(req, sh.all.data(), (uint32_t)(sh.all.size() / 4), &sh.tw, &sh.th)) {
     ctx->err = "tiles must be non-empty, in bounds and equal-sized";
     return IZPI_ERR_INVALID;
   }
-  // Several shares: deal quarter tiles (each even-sized tile of at least 16 x 16 pixels cut
-  // 2 x 2, in the tile's order), twice as many units to average the tiles' costs over: C3's
-  // eighth-shares' slowest against mean 1.016 / 1.021 over two runs against 1.035 / 1.017
-  // dealing whole tiles (0.816 / 0.811 of linear against 0.801 / 0.813; `profiles/r6ag/`,
-  // `r6ah/`). The image does not depend on the partition (per-sample streams).
-  if (n > 1 && tw % 2 == 0 && th % 2 == 0 && tw >= 16 && th >= 16) {
-    std::vector<uint32_t> sub;
-    sub.reserve(sh.all.size() * 4);
-    const uint32_t hw = tw / 2, hh = th / 2;
-    for (size_t t = 0; t + 3 < sh.all.size(); t += 4)
-      for (uint32_t j = 0; j < 2; j++)
-        for (uint32_t i = 0; i < 2; i++) {
-          const uint32_t x0 = sh.all[t] + i * hw, y0 = sh.all[t + 1] + j * hh;
-          sub.insert(sub.end(), {x0, y0, x0 + hw - 1, y0 + hh - 1});
-        }
-    sh.all.swap(sub);
-    tw = hw;
-    th = hh;
-  }
   sh.n = n;
-  const size_t ntiles = sh.all.size() / 4;
-  sh.block = share_block(ntiles, tw, th, n);
+  sh.block = share_block(sh.all.size() / 4, sh.tw, sh.th, n);
   return IZPI_OK;
 }
 
-// Render share r of the frame into ctx->d_share (stats in ctx->last).
-int render_share(izpi_ctx* ctx, const izpi_render_req* req, const Shares& sh, uint32_t r) {
+// The buffers of a share on this context: its block and, on the root, the gather buffer of
+// every share's block and (canvas_bytes != 0) the canvas in d_out.
+int share_buffers(izpi_ctx* ctx, const Shares& sh, bool root, size_t canvas_bytes = 0) {
   int rc = grow(ctx, (void**)&ctx->d_share, &ctx->share_cap, sh.block * sizeof(double));
-  if (rc) return rc;
+  if (!rc && root) rc = grow(ctx, (void**)&ctx->d_gather, &ctx->gather_cap, (size_t)sh.n * sh.block * sizeof(double));
+  if (!rc && root && canvas_bytes) rc = grow(ctx, (void**)&ctx->d_out, &ctx->out_cap, canvas_bytes);
+  return rc;
+}
+
+// Render share r of the frame into ctx->d_share (share_buffers; stats in ctx->last), or
+// with prepare_only allocate the workspace that render needs.
+int render_share(izpi_ctx* ctx, const izpi_render_req* req, const Shares& sh, uint32_t r, bool prepare_only = false) {
   const std::vector<uint32_t> mine = sh.mine(r);
   memset(&ctx->last, 0, sizeof(ctx->last));
-  if (mine.empty()) return IZPI_OK;  // more shares than tiles: an empty block joins the gather
-  izpi_render_req q = *req;
+  if (mine.empty()) return IZPI_OK;  // more shares than units: an empty block joins the gather
+  izpi_render_req q = request_copy(req);
   q.num_tiles = (uint32_t)(mine.size() / 4);
   q.tiles = mine.data();
   q.out_layout = IZPI_OUT_PACKED;
   q.post = IZPI_POST_NONE;
-  return render_impl(ctx, &q, ctx->d_share);
+  ctx->prepare_only = prepare_only;
+  const int rc = render_impl(ctx, &q, prepare_only ? nullptr : ctx->d_share);
+  ctx->prepare_only = false;
+  return rc;
 }
 
 // Root: scatter every share's packed tiles from d_gather into the canvas (row H - y,
@@ -823,12 +819,11 @@ int assemble(izpi_ctx* ctx, const izpi_render_req* req, const Shares& sh, double
   for (uint32_t r = 0; r < sh.n; r++) {
     const std::vector<uint32_t> t = sh.mine(r);
     if (t.empty()) continue;
-    const uint32_t nt = (uint32_t)(t.size() / 4), tw = t[2] - t[0] + 1, th = t[3] - t[1] + 1;
     int rc = grow(root, (void**)&root->d_utiles, &root->utiles_cap, sh.all.size() * sizeof(uint32_t));
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(root->d_utiles, t.data(), t.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    const uint32_t np = nt * tw * th;
-    hipLaunchKernelGGL(k_unpack, dim3((np + 255) / 256), dim3(256), 0, st, root->d_utiles, np, tw, th, req->width,
+    const uint32_t np = (uint32_t)(t.size() / 4) * sh.tw * sh.th;
+    hipLaunchKernelGGL(k_unpack, dim3((np + 255) / 256), dim3(256), 0, st, root->d_utiles, np, sh.tw, sh.th, req->width,
                        req->height, root->d_gather + (size_t)r * sh.block, canvas_dev);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));  // d_utiles is reused by the next share
@@ -846,6 +841,39 @@ struct izpi_multi {
   std::vector<izpi_ctx*> ctx;
   std::string err;
 };
+
+namespace {
+// The frame's shares over m's devices, with the root's (device 0's) buffers; the root's
+// device is left current.
+int multi_shares(izpi_multi* m, const izpi_render_req* req, Shares& sh) {
+  izpi_ctx* root = m->ctx[0];
+  int rc = make_shares(root, req, (uint32_t)m->ctx.size(), sh);
+  if (!rc && hipSetDevice(root->device) != hipSuccess) { root->err = "hipSetDevice"; rc = IZPI_ERR_HIP; }
+  if (!rc) rc = share_buffers(root, sh, true, (size_t)req->width * req->height * 4 * sizeof(double));
+  if (rc) m->err = root->err;
+  return rc;
+}
+
+// One host thread per device: fn(i, context i) with that device current. The first
+// failure in device order is the call's, reported in m->err.
+template <class F>
+int on_every_device(izpi_multi* m, F fn) {
+  const uint32_t G = (uint32_t)m->ctx.size();
+  std::vector<int> rcs(G, IZPI_OK);
+  std::vector<std::thread> th;
+  for (uint32_t i = 0; i < G; i++) {
+    th.emplace_back([&, i]() {
+      izpi_ctx* c = m->ctx[i];
+      if (hipSetDevice(c->device) != hipSuccess) { c->err = "hipSetDevice"; rcs[i] = IZPI_ERR_HIP; return; }
+      rcs[i] = fn(i, c);
+    });
+  }
+  for (std::thread& t : th) t.join();
+  for (uint32_t i = 0; i < G; i++)
+    if (rcs[i]) { m->err = "device " + std::to_string(i) + ": " + m->ctx[i]->err; return rcs[i]; }
+  return IZPI_OK;
+}
+}  // namespace
 
 extern "C" {
 
@@ -1344,26 +1372,16 @@ int izpi_gpu_render(izpi_ctx* ctx, const izpi_render_req* req, double* out_host,
 
 int izpi_gpu_prepare(izpi_ctx* ctx, const izpi_render_req* req) {
   if (!ctx) return IZPI_ERR_INVALID;
+  if (!req) { ctx->err = "null argument"; return IZPI_ERR_INVALID; }
   HIP_TRY(hipSetDevice(ctx->device));
-  izpi_render_req q = *req;
-  std::vector<uint32_t> mine;
   if (ctx->comm && ctx->comm_size > 1) {  // izpi_gpu_render_rank's share of the frame on this rank
     Shares sh;
     int rc = make_shares(ctx, req, ctx->comm_size, sh);
-    if (rc) return rc;
-    if ((rc = grow(ctx, (void**)&ctx->d_share, &ctx->share_cap, sh.block * sizeof(double)))) return rc;
-    if (ctx->comm_rank == 0 &&
-        (rc = grow(ctx, (void**)&ctx->d_gather, &ctx->gather_cap, (size_t)ctx->comm_size * sh.block * sizeof(double))))
-      return rc;
-    mine = sh.mine(ctx->comm_rank);
-    if (mine.empty()) return IZPI_OK;
-    q.num_tiles = (uint32_t)(mine.size() / 4);
-    q.tiles = mine.data();
-    q.out_layout = IZPI_OUT_PACKED;
-    q.post = IZPI_POST_NONE;
+    if (!rc) rc = share_buffers(ctx, sh, ctx->comm_rank == 0);
+    return rc ? rc : render_share(ctx, req, sh, ctx->comm_rank, true);
   }
   ctx->prepare_only = true;
-  const int rc = render_impl(ctx, &q, nullptr);
+  const int rc = render_impl(ctx, req, nullptr);
   ctx->prepare_only = false;
   return rc;
 }
@@ -1587,22 +1605,15 @@ int izpi_gpu_multi_upload_scene(izpi_multi* m, const izpi_scene_desc* scene) {
 
 int izpi_gpu_multi_render(izpi_multi* m, const izpi_render_req* req, double* out_host, izpi_render_stats* stats) {
   if (!m || m->ctx.empty()) return IZPI_ERR_INVALID;
-  const uint32_t G = (uint32_t)m->ctx.size();
   izpi_ctx* root = m->ctx[0];
   Shares sh;
-  int rc = make_shares(root, req, G, sh);
-  if (rc) { m->err = root->err; return rc; }
+  int rc = multi_shares(m, req, sh);
+  if (rc) return rc;
   if (req->post != IZPI_POST_NONE && req->num_tiles != 0) {
     m->err = "post-processing needs a whole-frame request";
     return IZPI_ERR_INVALID;
   }
   const size_t canvas_bytes = (size_t)req->width * req->height * 4 * sizeof(double);
-  if (hipSetDevice(root->device) != hipSuccess) { m->err = "hipSetDevice"; return IZPI_ERR_HIP; }
-  if ((rc = grow(root, (void**)&root->d_gather, &root->gather_cap, (size_t)G * sh.block * sizeof(double))) ||
-      (rc = grow(root, (void**)&root->d_out, &root->out_cap, canvas_bytes))) {
-    m->err = root->err;
-    return rc;
-  }
   // the caller's canvas is the starting point (pixels of no tile keep their values)
   if (out_host) {
     if (hipMemcpy(root->d_out, out_host, canvas_bytes, hipMemcpyHostToDevice) != hipSuccess) { m->err = "hipMemcpy"; return IZPI_ERR_HIP; }
@@ -1610,32 +1621,20 @@ int izpi_gpu_multi_render(izpi_multi* m, const izpi_render_req* req, double* out
     m->err = "hipMemset";
     return IZPI_ERR_HIP;
   }
-  // one host thread per device: render its share, then copy it into block i of the
-  // root's gather buffer (peer copy over xGMI; a plain device copy for the root)
-  std::vector<int> rcs(G, IZPI_OK);
-  std::vector<std::thread> th;
-  for (uint32_t i = 0; i < G; i++) {
-    th.emplace_back([&, i]() {
-      izpi_ctx* c = m->ctx[i];
-      if (hipSetDevice(c->device) != hipSuccess) { rcs[i] = IZPI_ERR_HIP; c->err = "hipSetDevice"; return; }
-      int r = render_share(c, req, sh, i);
-      if (!r) {
-        hipError_t e = hipMemcpyPeerAsync(root->d_gather + (size_t)i * sh.block, root->device, c->d_share, c->device,
-                                          sh.block * sizeof(double), c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) { c->err = std::string("gather copy: ") + hipGetErrorString(e); r = IZPI_ERR_HIP; }
-      }
-      rcs[i] = r;
-    });
-  }
-  for (std::thread& t : th) t.join();
-  for (uint32_t i = 0; i < G; i++) {
-    if (stats) stats[i] = m->ctx[i]->last;
-    if (rcs[i]) {
-      m->err = "device " + std::to_string(i) + ": " + m->ctx[i]->err;
-      return rcs[i];
-    }
-  }
+  // every device renders its share, then copies it into block i of the root's gather
+  // buffer (peer copy over xGMI; a plain device copy for the root)
+  rc = on_every_device(m, [&](uint32_t i, izpi_ctx* c) {
+    int r = share_buffers(c, sh, false);
+    if (!r) r = render_share(c, req, sh, i);
+    if (r) return r;
+    hipError_t e = hipMemcpyPeerAsync(root->d_gather + (size_t)i * sh.block, root->device, c->d_share, c->device,
+                                      sh.block * sizeof(double), c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) { c->err = std::string("gather copy: ") + hipGetErrorString(e); return (int)IZPI_ERR_HIP; }
+    return (int)IZPI_OK;
+  });
+  for (size_t i = 0; stats && i < m->ctx.size(); i++) stats[i] = m->ctx[i]->last;
+  if (rc) return rc;
   if (hipSetDevice(root->device) != hipSuccess) { m->err = "hipSetDevice"; return IZPI_ERR_HIP; }
   if ((rc = assemble(root, req, sh, root->d_out))) { m->err = root->err; return rc; }
   if (out_host && hipMemcpy(out_host, root->d_out, canvas_bytes, hipMemcpyDeviceToHost) != hipSuccess) {
@@ -1645,46 +1644,20 @@ int izpi_gpu_multi_render(izpi_multi* m, const izpi_render_req* req, double* out
   return IZPI_OK;
 }
 
-// ------------------------------------------ multi-GPU, one process per GPU
 int izpi_gpu_multi_prepare(izpi_multi* m, const izpi_render_req* req) {
-  if (!m) return IZPI_ERR_INVALID;
-  izpi_ctx* c0 = m->ctx[0];
+  if (!m || m->ctx.empty()) return IZPI_ERR_INVALID;
+  if (!req) { m->err = "null argument"; return IZPI_ERR_INVALID; }
   Shares sh;
-  int rc = make_shares(c0, req, (uint32_t)m->ctx.size(), sh);
-  if (rc) { m->err = c0->err; return rc; }
-  const uint32_t G = (uint32_t)m->ctx.size();
-  if (hipSetDevice(c0->device) != hipSuccess) { m->err = "hipSetDevice"; return IZPI_ERR_HIP; }
-  if ((rc = grow(c0, (void**)&c0->d_gather, &c0->gather_cap, (size_t)G * sh.block * sizeof(double))) ||
-      (rc = grow(c0, (void**)&c0->d_out, &c0->out_cap, (size_t)req->width * req->height * 4 * sizeof(double)))) {
-    m->err = c0->err;
-    return rc;
-  }
-  // the devices' workspaces, one host thread each (as izpi_gpu_multi_render renders them)
-  std::vector<int> rcs(G, IZPI_OK);
-  std::vector<std::thread> th;
-  for (uint32_t i = 0; i < G; i++) {
-    th.emplace_back([&, i]() {
-      izpi_ctx* c = m->ctx[i];
-      if (hipSetDevice(c->device) != hipSuccess) { c->err = "hipSetDevice"; rcs[i] = IZPI_ERR_HIP; return; }
-      int r = grow(c, (void**)&c->d_share, &c->share_cap, sh.block * sizeof(double));
-      const std::vector<uint32_t> mine = sh.mine(i);
-      if (r || mine.empty()) { rcs[i] = r; return; }
-      izpi_render_req q = *req;
-      q.num_tiles = (uint32_t)(mine.size() / 4);
-      q.tiles = mine.data();
-      q.out_layout = IZPI_OUT_PACKED;
-      q.post = IZPI_POST_NONE;
-      c->prepare_only = true;
-      rcs[i] = render_impl(c, &q, nullptr);
-      c->prepare_only = false;
-    });
-  }
-  for (std::thread& t : th) t.join();
-  for (uint32_t i = 0; i < G; i++)
-    if (rcs[i]) { m->err = "device " + std::to_string(i) + ": " + m->ctx[i]->err; return rcs[i]; }
-  return IZPI_OK;
+  const int rc = multi_shares(m, req, sh);
+  if (rc) return rc;
+  // the devices' workspaces, as izpi_gpu_multi_render renders them
+  return on_every_device(m, [&](uint32_t i, izpi_ctx* c) {
+    const int r = share_buffers(c, sh, false);
+    return r ? r : render_share(c, req, sh, i, true);
+  });
 }
 
+// ------------------------------------------ multi-GPU, one process per GPU
 int izpi_gpu_comm_id(uint8_t* id) {
   if (!id) return IZPI_ERR_INVALID;
   ncclUniqueId u;
@@ -1831,8 +1804,7 @@ int izpi_gpu_render_rank(izpi_ctx* ctx, const izpi_render_req* req, double* out_
   else if (ctx->comm_rank == 0 && !out_dev) { ctx->err = "rank 0 needs an output canvas"; prc = IZPI_ERR_INVALID; }
   else if (req && req->post != IZPI_POST_NONE && req->num_tiles != 0) { ctx->err = "post-processing needs a whole-frame request"; prc = IZPI_ERR_INVALID; }
   if (!prc) prc = make_shares(ctx, req, ctx->comm_size, sh);
-  if (!prc) prc = grow(ctx, (void**)&ctx->d_share, &ctx->share_cap, sh.block * sizeof(double));
-  if (!prc && ctx->comm_rank == 0) prc = grow(ctx, (void**)&ctx->d_gather, &ctx->gather_cap, (size_t)ctx->comm_size * sh.block * sizeof(double));
+  if (!prc) prc = share_buffers(ctx, sh, ctx->comm_rank == 0);
   if (prc == IZPI_OK && ctx->fault_inject == 1) { ctx->err = "injected fault before rendering"; prc = IZPI_ERR_DEVICE; }
   const std::string local_err = ctx->err;
   int worst = 0;

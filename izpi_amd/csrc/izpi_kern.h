@@ -37,6 +37,7 @@
 #include "../../include/izpi_host.h"
 #include "../../include/izpi_gpu_debug.h"
 #include "izpi_dev.h"
+#include "izpi_req.h"
 #include "cie_tables.h"
 
 using namespace izd;
@@ -1547,17 +1548,8 @@ struct Tracer {
   size_t spill_bytes = 0;  // the per-thread traversal-stack spill area this launch needs
 };
 
-// The request's tuning. ABI 1's izpi_render_tuning ended at tail_paths (an ABI-1 request,
-// abi_version 0, has its tuning pointer at the same place): its fields are read and the
-// later ones keep their defaults.
+// (the request's tuning across ABI versions: tuning_of, izpi_req.h)
 const izpi_render_tuning kDefaultTuning{};
-inline izpi_render_tuning tuning_of(const izpi_render_req* req) {
-  izpi_render_tuning t{};
-  if (!req || !req->tuning) return t;
-  if (req->abi_version >= 2) return *req->tuning;
-  memcpy(&t, req->tuning, offsetof(izpi_render_tuning, tail_paths) + sizeof(t.tail_paths));
-  return t;
-}
 
 // trace.hip: pick the k_trace2 instance and its grid (no allocation: the caller grows d_spill
 // to t->spill_bytes; need_uv: the caller reads the hits' (u, v), WaveParams::hit_uv), and

@@ -6,9 +6,10 @@ float64 NRGBA canvas (H, W, 4) the Go renderer fills — RGB for the Colour samp
 before post-processing for the Spectral sampler (``.render_spectral_rgb()`` applies
 FireflyRejection + XYZToRGB on the GPU like renderer.go:216-219).
 
-Multi-GPU goes through the library (include/izpi_gpu.h): tiles are dealt round-robin
-(tile_id % G == i), each device renders its tiles into a packed buffer, and the shares
-are gathered to device 0, which scatters them into the canvas. Two forms:
+Multi-GPU goes through the library (include/izpi_gpu.h): the frame's tiles become the units
+of izpi_host_share_units (quarter tiles, where they can be cut), the units are dealt
+round-robin (unit % G == i), each device renders its units into a packed buffer, and the
+shares are gathered to device 0, which scatters them into the canvas. Two forms:
 
 * ``MultiGPURenderer`` — one process drives every GPU (izpi_gpu_multi_*): one host
   thread and stream per device, xGMI peer copies to device 0;
@@ -303,8 +304,9 @@ class GPURenderer:
 
 class MultiGPURenderer:
     """Render over several GPUs from one process (izpi_gpu_multi_*): the scene is
-    replicated on every device, the frame's tiles are dealt tile % G, device 0 gathers
-    and assembles the canvas. Same arguments as GPURenderer plus ``devices``."""
+    replicated on every device, the frame's units (izpi_host_share_units: its tiles, cut
+    into quarters where they can be) are dealt unit % G, device 0 gathers and assembles the
+    canvas (sharding.py names the steps). Same arguments as GPURenderer plus ``devices``."""
 
     def __init__(self, scene, width, height, spp, devices, max_depth=50, sampler=N.SAMPLER_COLOUR,
                  background=(0.0, 0.0, 0.0), spectral_background=None, seed=12345, bvh_seed=12345, bvh="gpu",

@@ -1,22 +1,39 @@
 """Tile sharding across GPUs (one process per GPU) and the framebuffer gather.
 
 renderer.go:172-188 feeds tiles to workers dynamically; here the partition is static
-and interleaved — tile i goes to rank i % world — so centre tiles (dragon, glass) are
-spread over all ranks. Per pixel-sample RNG streams make every pixel independent of
-the partition, so the gathered canvas is bit-identical for any world size.
+and interleaved. The frame's tiles first become the units that are dealt
+(:func:`share_units`: with several ranks every tile that can be cut is cut into its four
+quarters), then unit u goes to rank u % world (:func:`shard_tiles`), so centre tiles
+(dragon, glass) are spread over all ranks. Per pixel-sample RNG streams make every pixel
+independent of the partition, so the gathered canvas is bit-identical for any world size.
 
-Each rank packs its tiles contiguously (IZPI_OUT_PACKED: tile after tile, rows of
+Each rank packs its units contiguously (IZPI_OUT_PACKED: unit after unit, rows of
 sample y, 4 doubles per pixel). One collective moves them to rank 0: ``dist.gather``
-of equal-sized (padded) packed buffers — over RCCL/xGMI with the "nccl" backend, or
-gloo in the CPU tests. Rank 0 scatters them into the canvas (k_unpack on the GPU;
-:func:`assemble` = izpi_host_assemble_shares, the library's host twin of it).
+of equal-sized (padded, :func:`packed_len`) packed buffers — over RCCL/xGMI with the
+"nccl" backend, or gloo in the CPU tests. Rank 0 scatters them into the canvas (k_unpack
+on the GPU; :func:`assemble` = izpi_host_assemble_shares, the library's host twin of it).
+These are the library's own steps (include/izpi_host.h): izpi_gpu_multi_render and
+izpi_gpu_render_rank run share_units -> shard_tiles -> packed_len -> render packed ->
+assemble, the last on the device.
 """
 import numpy as np
 
 
+def share_units(all_tiles, world):
+    """The units a frame's tiles are dealt in over `world` shares (izpi_host_share_units):
+    the quarters of every tile (tile order, then rows, then columns) when world > 1 and the
+    tiles are equal-sized, even in both extents and at least 16 x 16; else the tiles."""
+    from . import _native as N
+    t = np.ascontiguousarray(np.asarray(all_tiles, np.uint32).reshape(-1, 4))
+    out = np.zeros((4 * len(t), 4), np.uint32)
+    n = N.lib().izpi_host_share_units(t.ctypes.data_as(N.c_uint32_p), len(t), world, out.ctypes.data_as(N.c_uint32_p))
+    return np.ascontiguousarray(out[:n])
+
+
 def shard_tiles(all_tiles, rank, world):
-    """Tiles of share `rank` of `world`: the library's own rule (izpi_host_share_tiles),
-    the one izpi_gpu_multi_render and izpi_gpu_render_rank deal the frame with."""
+    """The units of share `rank` of `world` (`all_tiles`: the units, share_units): the
+    library's own rule (izpi_host_share_tiles), the one izpi_gpu_multi_render and
+    izpi_gpu_render_rank deal them with. Any tile list is dealt the same way."""
     import ctypes as C
     from . import _native as N
     t = np.ascontiguousarray(np.asarray(all_tiles, np.uint32).reshape(-1, 4))
@@ -33,8 +50,8 @@ def tile_pixels(tiles):
 
 
 def packed_len(all_tiles, world):
-    """Doubles per rank's (padded) packed buffer: the library's share block
-    (izpi_host_share_block: max tiles per rank * tile pixels * 4)."""
+    """Doubles per rank's (padded) packed buffer (`all_tiles`: the units, share_units):
+    the library's share block (izpi_host_share_block: max units per rank * unit pixels * 4)."""
     from . import _native as N
     t = np.asarray(all_tiles, np.int64)
     return int(N.lib().izpi_host_share_block(len(t), int(t[0, 2] - t[0, 0] + 1), int(t[0, 3] - t[0, 1] + 1), world))
@@ -42,7 +59,8 @@ def packed_len(all_tiles, world):
 
 def assemble(all_tiles, world, gathered, width, height, canvas=None):
     """Rank 0's assembly of the gathered share blocks (`world` blocks of packed_len
-    doubles, in rank order) into the canvas: the library's izpi_host_assemble_shares, the
+    doubles, in rank order; `all_tiles`: the units, share_units) into the canvas: the
+    library's izpi_host_assemble_shares, the
     host twin of what izpi_gpu_render_rank's root runs on the device (k_unpack)."""
     from . import _native as N
     t = np.ascontiguousarray(np.asarray(all_tiles, np.uint32).reshape(-1, 4))

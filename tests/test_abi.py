@@ -43,6 +43,36 @@ def test_struct_layouts_match():
     assert C.sizeof(N.BVH4Node) == 128  # == hitable.BVH4Node (bvh4.go:23-39)
 
 
+def test_older_abi_requests_are_read_within_their_size(tmp_path):
+    """request_copy and tuning_of (izpi_amd/csrc/izpi_req.h, the library's only readers of a
+    caller's request as a whole) on heap blocks of exactly an older ABI's size, in a
+    stand-alone program under AddressSanitizer and UBSan: no read past the caller's object,
+    and a request below ABI 3 renders IZPI_ACC_RECURSIVE whatever lies behind it."""
+    exe = tmp_path / "abi_prefix_check"
+    subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-Wall", "-Werror", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=all", "-o", str(exe), str(ROOT / "tests" / "abi_prefix_check.cpp")], check=True)
+    run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
+    assert run.returncode == 0, run.stderr[-3000:]
+    rows = {}
+    for line in run.stdout.splitlines():
+        name, *fields = line.split()
+        rows[name] = dict(f.split("=") for f in fields)
+    assert sorted(rows) == ["abi0", "abi0_no_tuning", "abi2", "abi3"]
+    for name, r in rows.items():
+        abi = 3 if name == "abi3" else 2 if name == "abi2" else 0
+        assert r["abi"] == str(abi)
+        # the caller's prefix, up to `tuning`
+        assert (r["width"], r["height"], r["spp"], r["seed"], r["exposure"], r["tuning"]) == ("64", "48", "7", "12345", "1.5", "1")
+        assert (int(r["sampler"]), int(r["post"])) == (N.SAMPLER_SPECTRAL, N.POST_SPECTRAL)
+        assert int(r["accumulation"]) == (N.ACC_FORWARD if abi >= 3 else N.ACC_RECURSIVE) and r["pad_req"] == "0"
+        # the tuning: ABI 1's ends at tail_paths, the later fields keep their defaults
+        if name == "abi0_no_tuning":
+            assert (r["slots"], r["flags"], r["tail_paths"], r["peer_timeout_ms"]) == ("0", "0", "0", "0")
+        else:
+            assert (r["slots"], int(r["flags"]), r["tail_paths"]) == ("300", N.TUNE_NO_TAIL, "99")
+            assert r["peer_timeout_ms"] == ("4000" if abi >= 2 else "0")
+
+
 def test_open_without_gpu_fails_cleanly():
     import ctypes as C
     try:

@@ -1,8 +1,9 @@
 """bench.py's launcher plumbing on CPU (no GPU work, --dry-run): `--gpus N` without
 torchrun is one process driving N GPUs (mode "threads"), torchrun is one rank per GPU
 (mode "ranks", gloo for the launcher's barrier and max of times). Both must report
-n_gpus = N and deal every tile of the frame to exactly one share, with the library's
-own share rule (izpi_host_share_tiles)."""
+n_gpus = N and deal every tile of the frame to exactly one share with the library's
+izpi_host_share_tiles. The dry run deals whole tiles: a coverage check of that function,
+not the partition a render uses (the units of izpi_host_share_units, tests/test_sharding.py)."""
 import json
 import socket
 import subprocess

@@ -1,10 +1,11 @@
-"""Multi-rank path on CPU (gloo, world_size 2 and 3): the library's own share rule
-(izpi_host_share_tiles), padded block size (izpi_host_share_block) and root assembly
-(izpi_host_assemble_shares, the host twin of the device's k_unpack step in
-izpi_gpu_render_rank), with the blocks moved by a gloo gather and fed by oracle renders of
-each rank's tiles. The assembled canvas must be bit-identical to a single-rank render:
-per pixel-sample RNG streams make the image partition-independent; a
-Python restatement of the unpack rule cross-checks the library's."""
+"""Multi-rank path on CPU (gloo, world_size 2, 3 and 8): the library's own share plan,
+the one izpi_gpu_render_rank runs — the units the frame is dealt in
+(izpi_host_share_units), their deal (izpi_host_share_tiles), the padded block size
+(izpi_host_share_block) and root assembly (izpi_host_assemble_shares, the host twin of
+the device's k_unpack step) — with the blocks moved by a gloo gather and fed by oracle
+renders of each rank's units. The assembled canvas must be bit-identical to a single-rank
+render: per pixel-sample RNG streams make the image partition-independent (SURVEY.md
+§8(e)); a Python restatement of the unpack rule cross-checks the library's."""
 import os
 import socket
 
@@ -12,7 +13,6 @@ import numpy as np
 import pytest
 import torch.multiprocessing as mp
 
-W = H = 64
 SPP = 3
 
 
@@ -24,7 +24,7 @@ def _free_port():
     return p
 
 
-def _oracle_render(tiles):
+def _oracle_render(tiles, W, H):
     import ctypes as C
     from izpi_amd import _native as N
     from izpi_amd import configs
@@ -38,7 +38,7 @@ def _oracle_render(tiles):
     return canvas.reshape(H, W, 4)
 
 
-def _worker(rank, world, port, outdir):
+def _worker(rank, world, port, outdir, W, H):
     import sys
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import torch
@@ -46,11 +46,11 @@ def _worker(rank, world, port, outdir):
     from izpi_amd import sharding
     from oracle import oracle as O
     dist.init_process_group("gloo", init_method="tcp://127.0.0.1:%d" % port, rank=rank, world_size=world)
-    all_tiles = O.tiles(W, H)
+    all_tiles = sharding.share_units(O.tiles(W, H), world)  # (named as before: the units from here on)
     mine = sharding.shard_tiles(all_tiles, rank, world)
     packed = np.zeros(sharding.packed_len(all_tiles, world))
     if len(mine):
-        part = sharding.pack_from_canvas(_oracle_render(mine), mine, H)
+        part = sharding.pack_from_canvas(_oracle_render(mine, W, H), mine, H)
         packed[:part.size] = part
     got = sharding.gather_packed(torch.from_numpy(packed), rank, world)
     if rank == 0:
@@ -67,11 +67,27 @@ def _worker(rank, world, port, outdir):
     dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("world", [2, 3])
-def test_sharded_gather_is_partition_independent(tmp_path, world):
+def _check_world(tmp_path, world, size, share_lens):
+    from izpi_amd import sharding
     from oracle import oracle as O
-    mp.spawn(_worker, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=True)
+    W = H = size
+    units = sharding.share_units(O.tiles(W, H), world)
+    assert sorted({len(sharding.shard_tiles(units, r, world)) for r in range(world)}) == share_lens
+    mp.spawn(_worker, args=(world, _free_port(), str(tmp_path), W, H), nprocs=world, join=True)
     got = np.load(tmp_path / ("canvas_%d.npy" % world))
-    full = _oracle_render(O.tiles(W, H))
+    full = _oracle_render(O.tiles(W, H), W, H)
     assert got.tobytes() == full.tobytes()
     assert np.all(full[0] == 0) and np.all(full[1:, :, 3] == 1.0)
+
+
+@pytest.mark.parametrize("world", [2, 3, 8])
+def test_sharded_gather_is_partition_independent(tmp_path, world):
+    """64 x 64: 16 units of 16 x 16 in shares of 8, of 6 and 5, and of 2."""
+    _check_world(tmp_path, world, 64, {2: [8], 3: [5, 6], 8: [2]}[world])
+
+
+@pytest.mark.parametrize("size,share_lens", [(96, [4, 5]), (50, [0, 1])])
+def test_sharded_gather_padded_and_empty_shares(tmp_path, size, share_lens):
+    """Eight ranks. 96 x 96: 36 units in shares of 5 and 4, so the blocks are padded.
+    50 x 50: 4 uncut tiles, so four ranks post empty (zero) blocks."""
+    _check_world(tmp_path, 8, size, share_lens)

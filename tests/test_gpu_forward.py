@@ -209,8 +209,9 @@ def test_forward_max_depth(gpu, max_depth):
 
 def test_forward_tiles_packed_and_shares(gpu):
     """A tile subset, packed into device memory and unpacked, and the eighth-shares of a
-    frame (izpi_host_share_tiles' deal) in forward mode: each equals the oracle's forward
-    form on the same tiles, and the shares assemble into the whole frame's canvas."""
+    frame (the shipped ones: izpi_host_share_tiles' deal of izpi_host_share_units' quarter
+    tiles) in forward mode: each equals the oracle's forward form on the same tiles, and the
+    shares assemble into the whole frame's canvas."""
     import torch
     from izpi_amd import sharding
     scene, W, H, spp, sampler = scene_case("glass_rgb_beer")
@@ -219,8 +220,10 @@ def test_forward_tiles_packed_and_shares(gpu):
     whole = r.render()
     tiles = common_tiles(W, H)
     canvas = torch.zeros((H, W, 4), dtype=torch.float64, device="cuda:0")
+    units = sharding.share_units(tiles, 8)
+    assert len(units) == 4 * len(tiles)
     for rank in range(8):
-        mine = sharding.shard_tiles(tiles, rank, 8)
+        mine = sharding.shard_tiles(units, rank, 8)
         packed = torch.zeros(r.output_doubles(mine, N.OUT_PACKED), dtype=torch.float64, device="cuda:0")
         r.render_device(packed.data_ptr(), tiles=mine, layout=N.OUT_PACKED)
         r.unpack(mine, packed.data_ptr(), canvas.data_ptr())

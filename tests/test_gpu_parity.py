@@ -701,21 +701,84 @@ def test_render_on_gpu_built_bvh_bitwise(gpu, which, quantized):
     r.close()
 
 
-@pytest.mark.parametrize("devices", [[0], [0, 0], [0, 0, 0]])
-def test_multi_gpu_render_bitwise(gpu, devices):
-    """izpi_gpu_multi_render (one call, one context per device, shares gathered to device
-    0) == the oracle, for 1-3 contexts (several contexts on this box's one GPU exercise
-    the share dealing, the padded gather and the assembly)."""
-    from izpi_amd.renderer import MultiGPURenderer
-    scene = configs.cornell_dragon(1.0, n=40)
-    r = MultiGPURenderer(scene, 64, 64, 4, devices, bvh="reference")
+_MULTI_REF = {}
+
+
+def multi_gpu_case(W, H, spp):
+    """The multi-GPU tests' scene and its oracle render (canvas, stats), computed once per frame size."""
+    if (W, H, spp) not in _MULTI_REF:
+        scene = configs.cornell_dragon(1.0, n=40)
+        _MULTI_REF[(W, H, spp)] = (scene,) + tuple(oracle_canvas(scene, W, H, spp, N.SAMPLER_COLOUR))
+    return _MULTI_REF[(W, H, spp)]
+
+
+def check_multi_gpu_render(devices, W, H, spp=4):
+    """izpi_gpu_multi_render == the oracle, and every device rendered the share the host
+    plan gives it (izpi_host_share_units dealt by izpi_host_share_tiles): its `samples`
+    are spp x every pixel of its units."""
+    from izpi_amd import sharding
+    from izpi_amd.renderer import MultiGPURenderer, common_tiles
+    scene, ref, ostats = multi_gpu_case(W, H, spp)
+    r = MultiGPURenderer(scene, W, H, spp, devices, bvh="reference")
     img = r.render()
-    ref, ostats = oracle_canvas(scene, 64, 64, 4, N.SAMPLER_COLOUR)
     assert_parity(img, ref)
     for k in ("rays", "node_visits", "tri_tests", "light_tri_tests", "samples"):
         assert sum(st[k] for st in r.stats) == ostats[k], k
-    assert len(r.stats) == len(devices)
+    G = len(devices)
+    assert len(r.stats) == G
+    units = sharding.share_units(common_tiles(W, H), G)
+    for i in range(G):
+        mine = sharding.shard_tiles(units, i, G)
+        assert r.stats[i]["samples"] == spp * (sharding.tile_pixels(mine) if len(mine) else 0), i
     r.close()
+
+
+@pytest.mark.parametrize("devices", [[0], [0, 0], [0, 0, 0], [0] * 8])
+def test_multi_gpu_render_bitwise(gpu, devices):
+    """izpi_gpu_multi_render (one call, one context per device, shares gathered to device
+    0) == the oracle, for 1-3 and 8 contexts (several contexts on this box's one GPU
+    exercise the share dealing, the padded gather and the assembly). 64 x 64 is 16 units of
+    16 x 16: three devices render 1536 / 1280 / 1280 pixels (whole tiles: 2048 / 1024 / 1024)."""
+    check_multi_gpu_render(devices, 64, 64)
+
+
+@pytest.mark.parametrize("size", [96, 50])
+def test_multi_gpu_render_padded_and_empty_shares(gpu, size):
+    """Eight contexts. 96 x 96: 36 units in shares of 5 and 4, so the gathered blocks are
+    padded. 50 x 50: tiles of 25 x 25 are not cut, so four devices hold empty shares."""
+    check_multi_gpu_render([0] * 8, size, size)
+
+
+def test_multi_gpu_prepare_eight_contexts(gpu):
+    """izpi_gpu_multi_prepare over 8 contexts: the frame after it allocates nothing on any
+    device (the bound of test_prepare_allocates_ahead_of_the_first_frame) and is the
+    unprepared renderer's canvas."""
+    from izpi_amd.renderer import MultiGPURenderer
+    scene = configs.cornell_dragon(1.0, n=40)
+    r = MultiGPURenderer(scene, 64, 64, 4, [0] * 8, bvh="reference")
+    r.prepare()
+    img = r.render()
+    for i, st in enumerate(r.stats):
+        assert st["alloc_ms"] < 0.5, (i, st["alloc_ms"])
+    r.close()
+    q = MultiGPURenderer(scene, 64, 64, 4, [0] * 8, bvh="reference")
+    assert q.render().tobytes() == img.tobytes()
+    q.close()
+
+
+def test_prepare_refuses_a_null_request(gpu):
+    """izpi_gpu_prepare and izpi_gpu_multi_prepare with a NULL request: IZPI_ERR_INVALID
+    ("null argument", as izpi_gpu_render), nothing dereferenced."""
+    from izpi_amd.renderer import MultiGPURenderer
+    scene = configs.cornell_rgb()
+    r = GPURenderer(scene, 24, 24, 2)
+    assert N.lib().izpi_gpu_prepare(r.ctx, None) == N.IZPI_ERR_INVALID
+    assert N.lib().izpi_gpu_last_error(r.ctx) == b"null argument"
+    r.close()
+    m = MultiGPURenderer(scene, 24, 24, 2, [0, 0], bvh="reference")
+    assert N.lib().izpi_gpu_multi_prepare(m.m, None) == N.IZPI_ERR_INVALID
+    assert N.lib().izpi_gpu_multi_last_error(m.m) == b"null argument"
+    m.close()
 
 
 def test_multi_gpu_spectral_post_bitwise(gpu):

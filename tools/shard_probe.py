@@ -1,7 +1,8 @@
 """Per-rank render time of a W-way tile shard on ONE GPU (strong-scaling probe).
 
 python tools/shard_probe.py --config C3 --worlds 1,2,4,8
-For each W, renders every rank's tiles (packed layout, device memory) and prints ms,
+For each W, renders every rank's share of the frame as the library deals it (the units of
+izpi_host_share_units dealt unit % W; packed layout, device memory) and prints ms,
 passes and the implied efficiency T(1) / (W * max rank time), i.e. the scaling the
 multi-GPU bench would see without the gather, split into the share imbalance
 (max / mean rank time) and the per-share overhead (W * mean / T(1))."""
@@ -26,7 +27,7 @@ def main():
     ap.add_argument("--ranks", default="", help="comma list of the ranks to render (default all)")
     ap.add_argument("--share-slots", default="", help="comma list: tuning slot caps tried for the shares of W > 1 (the W = 1 frame keeps the default)")
     ap.add_argument("--share-tunes", default="", help="semicolon list of 'field=value,...' tunings tried for the shares of W > 1")
-    ap.add_argument("--split", type=int, default=1, help="deal sub-tiles: each tile cut into split x split before dealing (W > 1)")
+    ap.add_argument("--split", type=int, default=None, choices=[1], help="1: deal whole tiles, for comparison (default: the library's units)")
     a = ap.parse_args()
     import torch
     from izpi_amd import _native as N
@@ -45,16 +46,6 @@ def main():
                     tuning=N.tuning(**tune) if tune else None,
                     accumulation=N.ACC_FORWARD if a.acc == "forward" else N.ACC_RECURSIVE)
     all_tiles = common_tiles(cfg.width, cfg.height)
-    import numpy as np
-    def split_tiles(tl, k):
-        out = []
-        for x0, y0, x1, y1 in np.asarray(tl).reshape(-1, 4):
-            w, h = (x1 - x0 + 1) // k, (y1 - y0 + 1) // k
-            for j in range(k):
-                for i in range(k):
-                    out.append((x0 + i * w, y0 + j * h, x0 + i * w + w - 1, y0 + j * h + h - 1))
-        return np.asarray(out, np.uint32)
-    deal_tiles = split_tiles(all_tiles, a.split) if a.split > 1 else all_tiles
     t1 = None
     base_tuning = r.tuning
     runs = [(int(x), None) for x in a.worlds.split(",")]
@@ -71,7 +62,7 @@ def main():
             r.tuning = N.tuning(**dict(tune, slots=sl))
         worst, times = 0.0, []
         for rank in ([int(x) for x in a.ranks.split(",")] if a.ranks and w > 1 else range(w)):
-            src = deal_tiles if w > 1 else all_tiles
+            src = all_tiles if a.split == 1 else sharding.share_units(all_tiles, w)
             mine = sharding.shard_tiles(src, rank, w)
             buf = torch.zeros(sharding.packed_len(src, w), dtype=torch.float64, device="cuda")
             r.render_device(buf.data_ptr(), tiles=mine, layout=N.OUT_PACKED)  # warm
