@@ -82,7 +82,28 @@ enum {
   IZPI_SCENE_QUANTIZED_BVH = 1
 };
 
-enum { IZPI_SAMPLER_COLOUR = 2, IZPI_SAMPLER_SPECTRAL = 5 }; /* sampler.go:13-20 */
+/* render.New's sampler types (sampler.go:13-20). Colour and Spectral trace paths. The other
+ * three are the preview samplers (render/rgb.go:27-41 around sampler/normal.go, albedo.go,
+ * wireframe.go): one primary ray per sample, the Colour sampler's own (same seed, same
+ * streams), max_depth and accumulation ignored, IZPI_POST_SPECTRAL refused:
+ *  NORMAL:    the closest hit's normal as Hit leaves it (normal-mapped, a sphere's flipped
+ *             towards the ray; components may be negative); a miss is (0, 0, 0).
+ *  ALBEDO:    Material.Albedo at the closest hit: the albedo texture (Lambertian, PBR,
+ *             Isotropic), the emit texture (DiffuseLight), Metal's albedo, (1, 1, 1) for a
+ *             Dielectric; a miss is (0, 0, 0). Needs the RGB textures the Colour sampler needs.
+ *  WIREFRAME: req->ink where HitableSlice.HitEdge (hitable_slice.go:48-70) reports an edge,
+ *             else req->background (the paper). HitEdge traverses twice, the second time up
+ *             to tMax = t + 2^-52, which is t itself from t = 4 upwards: a sphere hit that far
+ *             away then fails `temp < tMax` and the sample is paper. Both traversals run and
+ *             both count in node_visits / tri_tests / sph_tests.
+ * stats.rays == stats.samples for the three (numRays counts Sample calls). */
+enum {
+  IZPI_SAMPLER_NORMAL = 1,
+  IZPI_SAMPLER_COLOUR = 2,
+  IZPI_SAMPLER_WIREFRAME = 3,
+  IZPI_SAMPLER_ALBEDO = 4,
+  IZPI_SAMPLER_SPECTRAL = 5
+};
 enum {
   IZPI_OUT_CANVAS = 0, /* W*H*4 float64 NRGBA canvas; pixel (x,y) lands in row H-y (rgb.go:41) */
   IZPI_OUT_PACKED = 1  /* tiles packed in request order, each (x1-x0+1)*(y1-y0+1)*4,
@@ -137,17 +158,20 @@ typedef struct izpi_render_req {
   const uint32_t* tiles;      /* [num_tiles][4] = x0,y0,x1,y1 inclusive (workUnit, renderer.go:56-70) */
   const double* bg_spd_wavelengths; /* spectral background (Spectral.background) */
   const double* bg_spd_values;
-  double background[3];       /* Colour background (leader.go:140: black) */
+  double background[3];       /* Colour background (leader.go:140: black); the WireFrame sampler's paper */
   uint64_t seed;              /* master seed of the per-sample LCG streams */
   uint32_t post;              /* IZPI_POST_*: post-processing of a whole-frame IZPI_OUT_CANVAS render */
-  uint32_t abi_version;       /* IZPI_ABI_VERSION (3); 0 = a request laid out by ABI 1 (this field was padding):
+  uint32_t abi_version;       /* IZPI_ABI_VERSION (4); 0 = a request laid out by ABI 1 (this field was padding):
                                  its tuning, when set, is read as ABI 1's izpi_render_tuning, which ended at
                                  tail_paths; the later fields keep their defaults. A request of ABI 1 or 2
-                                 ends at `tuning`: it renders IZPI_ACC_RECURSIVE */
+                                 ends at `tuning`: it renders IZPI_ACC_RECURSIVE. A request of ABI 3 ends
+                                 at `pad_req`: its ink is black */
   double exposure;            /* XYZToRGB exposure (Scene.Exposure = camera exposure) */
   const izpi_render_tuning* tuning; /* NULL = defaults */
   uint32_t accumulation;      /* IZPI_ACC_* (ABI 3) */
   uint32_t pad_req;
+  double ink[3];              /* IZPI_SAMPLER_WIREFRAME: the edge colour (render.New's ink); the paper is
+                                 `background` (ABI 4) */
 } izpi_render_req;
 
 /* How a path's radiance is summed (izpi_render_req.accumulation). Both trace the same

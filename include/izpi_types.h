@@ -8,7 +8,7 @@
  *   material kinds  = transport.proto MaterialType (DIELECTRIC=1 … PBR=6)
  *   texture kinds   = transport.proto TextureType, with the SpectralConstant oneof
  *                     split into GAUSSIAN/TABULATED (texture/spectral_constant.go:65-106)
- *   sampler kinds   = sampler.go:13-20 (ColourSampler=2, SpectralSampler=5)
+ *   sampler kinds   = sampler.go:13-20 (Normal=1, Colour=2, WireFrame=3, Albedo=4, Spectral=5)
  */
 #ifndef IZPI_TYPES_H
 #define IZPI_TYPES_H
@@ -18,7 +18,7 @@
 extern "C" {
 #endif
 
-#define IZPI_ABI_VERSION 3u
+#define IZPI_ABI_VERSION 4u
 
 /* ---- status codes (0 = OK) ------------------------------------------------ */
 enum {

@@ -22,12 +22,15 @@
  *   With --ref-bvh the scene keeps the host's NewBVH4 tree (Options.BVH != BVHGPU): no
  *   SKIP_BVH flag and no GPU build. The request carries
  *   IZPI_ACC_FORWARD (Options.Accumulation's default), IZPI_ACC_RECURSIVE with --recursive.
+ *   --sampler NAME stands for Options.SamplerType (sampler.go:22-28: colour, normal,
+ *   wireframe, albedo, spectral; default: the scene's colour representation, as the leader
+ *   picks it), --ink r,g,b for Options.Ink.
  *   The replay is written in the subset tests/go_shim_sequence.py reads (calls of the
  *   library in plain statements and if conditions, no call inside a ?: arm), which checks
  *   that its call sequence is the shim's in every branch.
  *
  *   usage: go_shim_replay scene.izpi W H SPP out.f64 [--png-pipeline] [--devices 0,0,...]
- *                         [--bg-spd] [--tiles N] [--ref-bvh] [--recursive]
+ *                         [--bg-spd] [--tiles N] [--ref-bvh] [--recursive] [--sampler NAME] [--ink r,g,b]
  * Exit status 0 on success; the canvas is written as raw little-endian float64.
  */
 #include <stdint.h>
@@ -47,12 +50,18 @@ int main(int argc, char** argv) {
   if (argc < 6) return fail("usage", "go_shim_replay scene.izpi W H SPP out.f64 [--png-pipeline] [--devices a,b,..]");
   const uint32_t W = (uint32_t)atoi(argv[2]), H = (uint32_t)atoi(argv[3]), spp = (uint32_t)atoi(argv[4]);
   int png = 0, devices[16], ndev = 0, bg_spd = 0, ntiles = 0, ref_bvh = 0, recursive = 0;
+  const char* sampler_name = NULL;
+  double ink[3] = {0.0, 0.0, 0.0};
   for (int i = 6; i < argc; i++) {
     if (!strcmp(argv[i], "--png-pipeline")) png = 1;
     else if (!strcmp(argv[i], "--bg-spd")) bg_spd = 1;
     else if (!strcmp(argv[i], "--ref-bvh")) ref_bvh = 1;
     else if (!strcmp(argv[i], "--recursive")) recursive = 1;
     else if (!strcmp(argv[i], "--tiles") && i + 1 < argc) ntiles = atoi(argv[++i]);
+    else if (!strcmp(argv[i], "--sampler") && i + 1 < argc) sampler_name = argv[++i];
+    else if (!strcmp(argv[i], "--ink") && i + 1 < argc) {
+      if (sscanf(argv[++i], "%lf,%lf,%lf", &ink[0], &ink[1], &ink[2]) != 3) return fail("--ink", "takes r,g,b");
+    }
     else if (!strcmp(argv[i], "--devices") && i + 1 < argc) {
       for (char* t = strtok(argv[++i], ","); t && ndev < 16; t = strtok(NULL, ",")) devices[ndev++] = atoi(t);
     }
@@ -125,11 +134,18 @@ int main(int argc, char** argv) {
   req.exposure = desc->camera.exposure;
   req.accumulation = IZPI_ACC_FORWARD;
   if (recursive) req.accumulation = IZPI_ACC_RECURSIVE;
+  for (int i = 0; i < 3; i++) req.ink[i] = ink[i];
   uint32_t post = IZPI_POST_NONE;
-  req.sampler = IZPI_SAMPLER_COLOUR;
+  /* Options.SamplerType: the scene's colour representation (leader.go:77-81) unless named */
+  if (!sampler_name) sampler_name = info.colour_representation == IZPI_COLOUR_SPECTRAL ? "spectral" : "colour";
+  if (!strcmp(sampler_name, "normal")) req.sampler = IZPI_SAMPLER_NORMAL;
+  else if (!strcmp(sampler_name, "colour")) req.sampler = IZPI_SAMPLER_COLOUR;
+  else if (!strcmp(sampler_name, "wireframe")) req.sampler = IZPI_SAMPLER_WIREFRAME;
+  else if (!strcmp(sampler_name, "albedo")) req.sampler = IZPI_SAMPLER_ALBEDO;
+  else if (!strcmp(sampler_name, "spectral")) req.sampler = IZPI_SAMPLER_SPECTRAL;
+  if (req.sampler == 0) return fail("--sampler", "must be colour, normal, wireframe, albedo or spectral");
   double* bg = NULL;
-  if (info.colour_representation == IZPI_COLOUR_SPECTRAL) {  /* leader.go:77-81 */
-    req.sampler = IZPI_SAMPLER_SPECTRAL;
+  if (req.sampler == IZPI_SAMPLER_SPECTRAL) {
     post |= IZPI_POST_SPECTRAL;
     if (bg_spd) {  /* colours.SpectralBlack: 75 zeros at 380, 385, ... 750 nm */
       bg = (double*)malloc(2 * 75 * sizeof(double));
@@ -183,7 +199,7 @@ int main(int argc, char** argv) {
   izpi_host_scene_free(host);
   izpi_scene_free(ps);
   printf("{\"sampler\": \"%s\", \"devices\": %d, \"post\": %u, \"bg_spd\": %u, \"tiles\": %d, \"ref_bvh\": %d, \"recursive\": %d}\n",
-         req.sampler == IZPI_SAMPLER_SPECTRAL ? "spectral" : "colour", ndev > 1 ? ndev : 1, post, req.num_bg_spd, ntiles, ref_bvh,
+         sampler_name, ndev > 1 ? ndev : 1, post, req.num_bg_spd, ntiles, ref_bvh,
          recursive);
   return 0;
 }

@@ -79,9 +79,10 @@ const (
 // Options are the render.New parameters (renderer.go:73-104) the GPU path uses, plus the device.
 type Options struct {
 	SizeX, SizeY, NumSamples, MaxDepth int
-	Background                         [3]float64    // colours.Black in leader mode (leader.go:140)
+	Background                         [3]float64    // colours.Black in leader mode (leader.go:140); the WireFrame sampler's paper
+	Ink                                [3]float64    // render.New's ink: the WireFrame sampler's edge colour
 	SpectralBackground                 []float64     // 75 values at the CIE wavelengths, nil = black
-	SamplerType                        sampler.SamplerType
+	SamplerType                        sampler.SamplerType // any of the five (sampler.go:13-20)
 	Device                             int
 	Devices                            []int         // >1 entries: one Render fans out over these GPUs (izpi_gpu_multi_*)
 	Seed                               uint64        // master seed of the per-sample LCG streams
@@ -232,11 +233,26 @@ func New(protoScene *pb_transport.Scene, textures map[string]*texture.ImageTxt,
 	}
 	for i := 0; i < 3; i++ {
 		r.req.background[i] = C.double(opt.Background[i])
+		r.req.ink[i] = C.double(opt.Ink[i])
 	}
 	post := C.uint32_t(C.IZPI_POST_NONE)
-	r.req.sampler = C.IZPI_SAMPLER_COLOUR
-	if opt.SamplerType == sampler.SpectralSampler {
+	// the five SamplerTypes one to one (sampler.go:13-20 are the IZPI_SAMPLER_* values);
+	// any other is an error, as render.New's caller fatals on it (renderer.go:136)
+	if opt.SamplerType == sampler.NormalSampler {
+		r.req.sampler = C.IZPI_SAMPLER_NORMAL
+	} else if opt.SamplerType == sampler.ColourSampler {
+		r.req.sampler = C.IZPI_SAMPLER_COLOUR
+	} else if opt.SamplerType == sampler.WireFrameSampler {
+		r.req.sampler = C.IZPI_SAMPLER_WIREFRAME
+	} else if opt.SamplerType == sampler.AlbedoSampler {
+		r.req.sampler = C.IZPI_SAMPLER_ALBEDO
+	} else if opt.SamplerType == sampler.SpectralSampler {
 		r.req.sampler = C.IZPI_SAMPLER_SPECTRAL
+	}
+	if r.req.sampler == 0 { // sampler.InvalidSampler, or a value past the five
+		return nil, fmt.Errorf("invalid sampler type %v", opt.SamplerType)
+	}
+	if opt.SamplerType == sampler.SpectralSampler {
 		post |= C.IZPI_POST_SPECTRAL // FireflyRejection + XYZToRGB
 		if len(opt.SpectralBackground) == 75 { // e.g. colours.SpectralBlack in leader mode (leader.go:142)
 			r.bg = (*C.double)(C.malloc(C.size_t(2 * 75 * 8)))

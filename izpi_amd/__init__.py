@@ -6,4 +6,10 @@ C++ host scene producer of include/izpi_host.h), and this thin Python host mirro
 """
 from . import _native  # noqa: F401
 
-__all__ = ["_native", "scene", "configs", "renderer", "build"]
+# sampler.go:22-28 (samplerMap): the names izpi's --sampler takes and render.New's SamplerType
+# values, which are the IZPI_SAMPLER_* of include/izpi_gpu.h
+SAMPLERS = {"colour": _native.SAMPLER_COLOUR, "normal": _native.SAMPLER_NORMAL,
+            "wireframe": _native.SAMPLER_WIREFRAME, "albedo": _native.SAMPLER_ALBEDO,
+            "spectral": _native.SAMPLER_SPECTRAL}
+
+__all__ = ["_native", "scene", "configs", "renderer", "build", "SAMPLERS"]

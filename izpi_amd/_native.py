@@ -17,14 +17,14 @@ c_float_p = C.POINTER(C.c_float)
 # ---- include/izpi_types.h
 COMM_ID_BYTES = 128
 IZPI_OK, IZPI_ERR_INVALID, IZPI_ERR_HIP, IZPI_ERR_NO_SCENE, IZPI_ERR_UNSUPPORTED, IZPI_ERR_DEVICE, IZPI_ERR_PEER = range(7)
-IZPI_ABI_VERSION = 3
+IZPI_ABI_VERSION = 4
 ACC_RECURSIVE, ACC_FORWARD = 0, 1
 SCENE_QUANTIZED_BVH = 1
 PRIM_TRIANGLE, PRIM_SPHERE = 0, 1
 TEX_CONSTANT, TEX_IMAGE, TEX_SPECTRAL_GAUSSIAN, TEX_SPECTRAL_TABULATED, TEX_SPECTRAL_IMAGE = 1, 3, 5, 7, 9
 MAT_DIELECTRIC, MAT_DIFFUSE_LIGHT, MAT_ISOTROPIC, MAT_LAMBERT, MAT_METAL, MAT_PBR = 1, 2, 3, 4, 5, 6
 MATF_BEER_LAMBERT = 1
-SAMPLER_COLOUR, SAMPLER_SPECTRAL = 2, 5
+SAMPLER_NORMAL, SAMPLER_COLOUR, SAMPLER_WIREFRAME, SAMPLER_ALBEDO, SAMPLER_SPECTRAL = 1, 2, 3, 4, 5  # sampler.go:13-20
 OUT_CANVAS, OUT_PACKED = 0, 1
 POST_NONE, POST_SPECTRAL, POST_GAMMA_CLAMP = 0, 1, 2
 FILTER_GAMMA, FILTER_CLAMP = 1, 2
@@ -113,7 +113,8 @@ class RenderReq(C.Structure):
                 ("num_bg_spd", C.c_uint32), ("tiles", c_uint32_p), ("bg_spd_wavelengths", c_double_p),
                 ("bg_spd_values", c_double_p), ("background", C.c_double * 3), ("seed", C.c_uint64),
                 ("post", C.c_uint32), ("abi_version", C.c_uint32), ("exposure", C.c_double),
-                ("tuning", C.POINTER(RenderTuning)), ("accumulation", C.c_uint32), ("pad_req", C.c_uint32)]
+                ("tuning", C.POINTER(RenderTuning)), ("accumulation", C.c_uint32), ("pad_req", C.c_uint32),
+                ("ink", C.c_double * 3)]
 
 
 class RenderStats(C.Structure):

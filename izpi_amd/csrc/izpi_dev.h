@@ -84,6 +84,12 @@ struct alignas(16) GTriTex {
   double uv[6];     // u0, v0, u1, v1, u2, v2
   double tg[3], bt[3];
 };
+// A triangle's second and third vertex as uploaded, in BVH leaf order (GPrim holds v0 and the
+// edges): Triangle.HitEdge tests the hit point against the sides v0v1, v1v2, v2v0
+// (triangle.go:282-302), and v0 + e1 is not bit for bit v1. Read by the WireFrame sampler only.
+struct alignas(16) GTriVerts {
+  double v1[3], v2[3];
+};
 // Light record (Scene.Lights entry, transport order): everything PDFValue/Random read.
 struct alignas(16) GLight {
   double v0[3], v1[3], v2[3], e1[3], e2[3], n[3];  // triangle

@@ -433,6 +433,133 @@ int apply_post(izpi_ctx* ctx, const izpi_render_req* req, double* canvas_dev) {
   return IZPI_OK;
 }
 
+// The preview samplers' entries, `slots` of them, in izpi_ctx::d_state: returns the bytes
+// (base == nullptr) or fills pp.buf and pp.tminmax.
+size_t carve_preview(char* base, uint32_t slots, bool time, bool uv, bool wire, PreviewParams* pp) {
+  size_t off = 0;
+  auto take = [&](size_t bytes) -> char* {
+    char* p = base ? base + off : nullptr;
+    off += (bytes + 255) & ~(size_t)255;
+    return p;
+  };
+  WaveBuf w{};
+  w.ray = (RayOD*)take((size_t)slots * sizeof(RayOD));
+  w.kind = (uint32_t*)take((size_t)slots * sizeof(uint32_t));
+  w.time = time ? (double*)take((size_t)slots * sizeof(double)) : nullptr;
+  w.hs = uv ? 2u : 1u;  // (t, prim) and (u, v) interleaved, as carve_state
+  w.hit = (double2*)take((size_t)slots * w.hs * sizeof(double2));
+  w.huv = uv && w.hit ? w.hit + 1 : nullptr;
+  w.tplane = slots;
+  double2* tm = wire ? (double2*)take((size_t)slots * sizeof(double2)) : nullptr;
+  if (pp) { pp->buf = w; pp->tminmax = tm; pp->slots = slots; }
+  return off;
+}
+
+// render_body for the Normal, Albedo and WireFrame samplers, from the point where the
+// request is checked and its tiles and k_trace2 instance are known: a workspace of camera
+// rays, hits and per-sample results only (no records, pool, or second side of the state),
+// within the buffers a Colour render of this context may already hold (they only grow here).
+int preview_body(izpi_ctx* ctx, const izpi_render_req* req, const DevScene& sc, const Tracer& tr, const izpi_render_tuning& tu,
+                 const std::vector<uint32_t>& tiles, uint32_t tw, uint32_t th, uint32_t num_pixels, double* out_dev) {
+  const bool wire = req->sampler == IZPI_SAMPLER_WIREFRAME;
+  const bool need_time = !ctx->sc.tri_only, need_uv = !ctx->sc.tri_only || ctx->any_uv;
+  const uint64_t size_key[8] = {num_pixels, req->spp, req->sampler, tu.slots, tu.chunk_units, 0, 0, 0};
+  const bool reuse = ctx->pv_sizing_valid && memcmp(size_key, ctx->pv_sizing.key, sizeof(size_key)) == 0;
+  uint32_t chunk = ctx->pv_sizing.chunk, slots = ctx->pv_sizing.slots;
+  if (!reuse) {
+    // as render_body: per-sample results within 1/8 of the HBM this context may use, the
+    // entries within the rest of 15/32 of it
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
+    const uint64_t avail = free_b ? ((uint64_t)free_b + render_buffer_bytes(ctx)) / std::max(1u, ctx->dev_share) : 0;
+    uint64_t max_units = std::max<uint64_t>(64ull << 20, (avail / 8) / (SMP_D * sizeof(double)));
+    if (tu.chunk_units) max_units = tu.chunk_units;
+    chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(req->spp, max_units / num_pixels));
+    const uint32_t nchunks = (req->spp + chunk - 1) / chunk;
+    chunk = (req->spp + nchunks - 1) / nchunks;
+    uint64_t slot_cap = 256ull << 20;
+    if (tu.slots) slot_cap = std::max<uint64_t>(1024, tu.slots);
+    const uint64_t per_slot = carve_preview(nullptr, 1024, need_time, need_uv, wire, nullptr) / 1024 + 1;
+    const uint64_t samples_bytes = (uint64_t)num_pixels * chunk * SMP_D * sizeof(double), budget = avail / 32 * 15;
+    if (avail > 0) slot_cap = std::min<uint64_t>(slot_cap, std::max<uint64_t>(1024, (budget > samples_bytes ? budget - samples_bytes : 0) / per_slot));
+    slots = (uint32_t)std::min<uint64_t>((uint64_t)num_pixels * chunk, slot_cap);
+    memcpy(ctx->pv_sizing.key, size_key, sizeof(size_key));
+    ctx->pv_sizing.chunk = chunk; ctx->pv_sizing.slots = slots;
+    ctx->pv_sizing_valid = true;
+  }
+  const auto t_alloc0 = std::chrono::steady_clock::now();
+  const size_t samples_bytes = (size_t)num_pixels * chunk * SMP_D * sizeof(double);
+  const size_t state_bytes = carve_preview(nullptr, slots, need_time, need_uv, wire, nullptr);
+  const uint32_t cpart_rows = ctx->num_cus * CPART_BLOCKS_PER_CU * 4u;
+  int rc;
+  if ((rc = grow(ctx, (void**)&ctx->d_samples, &ctx->samples_cap, samples_bytes)) ||
+      (rc = grow(ctx, (void**)&ctx->d_running, &ctx->running_cap, (size_t)num_pixels * 3 * sizeof(double))) ||
+      (rc = grow(ctx, (void**)&ctx->d_state, &ctx->state_cap, state_bytes)) ||
+      (rc = grow(ctx, (void**)&ctx->d_spill, &ctx->spill_cap, tr.spill_bytes)) ||
+      (rc = grow(ctx, (void**)&ctx->d_tiles, &ctx->tiles_cap, tiles.size() * sizeof(uint32_t))) ||
+      (rc = grow(ctx, (void**)&ctx->d_cpart, &ctx->cpart_cap, (size_t)cpart_rows * CNT_N * sizeof(unsigned long long)))) {
+    ctx->pv_sizing_valid = false;
+    return rc;
+  }
+  const double alloc_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_alloc0).count();
+  hipStream_t st = ctx->stream;
+  if (ctx->prepare_only) {  // izpi_gpu_prepare: the device's first work on the workspace, as render_body
+    HIP_TRY(hipMemsetAsync(ctx->d_state, 0, state_bytes, st));
+    HIP_TRY(hipMemsetAsync(ctx->d_samples, 0, samples_bytes, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    ctx->last = izpi_render_stats{};
+    ctx->last.workspace_bytes = workspace_bytes(ctx);
+    ctx->last.slots = slots; ctx->last.chunk_spp = chunk; ctx->last.alloc_ms = alloc_ms;
+    return IZPI_OK;
+  }
+  HIP_TRY(hipMemcpyAsync(ctx->d_tiles, tiles.data(), tiles.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(ctx->d_running, 0, (size_t)num_pixels * 3 * sizeof(double), st));
+  HIP_TRY(hipMemsetAsync(ctx->d_counters, 0, CNT_N * sizeof(unsigned long long), st));
+  HIP_TRY(hipMemsetAsync(ctx->d_cpart, 0, (size_t)cpart_rows * CNT_N * sizeof(unsigned long long), st));
+  HIP_TRY(hipMemsetAsync(ctx->d_misc, 0, 8 * MISC_STRIDE * sizeof(uint32_t), st));
+  ShadeParams sp{};
+  sp.width = req->width; sp.height = req->height; sp.tile_w = tw; sp.tile_h = th; sp.slots = slots;
+  sp.max_depth = 1;  // (the request's is ignored; start_path completes a sample of max_depth 0 at once)
+  sp.tiles = ctx->d_tiles; sp.seed = req->seed; sp.out = ctx->d_samples;
+  sp.background[0] = req->background[0]; sp.background[1] = req->background[1]; sp.background[2] = req->background[2];
+  sp.counters = ctx->d_counters; sp.cpart = ctx->d_cpart; sp.error = misc(ctx, 1);
+  PreviewParams pp{};
+  carve_preview(ctx->d_state, slots, need_time, need_uv, wire, &pp);
+  pp.verts = ctx->d_triverts;
+  if (req->abi_version >= 4)  // (a request of ABI 3 ends before `ink`: black)
+    for (int k = 0; k < 3; k++) pp.ink[k] = req->ink[k];
+  AccumParams ap{};
+  ap.num_pixels = num_pixels; ap.spp = req->spp; ap.width = req->width; ap.height = req->height;
+  ap.tile_w = tw; ap.tile_h = th; ap.sampler = IZPI_SAMPLER_COLOUR;  // col / numSamples (rgb.go:38)
+  ap.out_layout = req->out_layout;
+  ap.tiles = ctx->d_tiles; ap.samples = ctx->d_samples; ap.running = ctx->d_running; ap.out = out_dev;
+  float trace_ms = 0, shade_ms = 0, total_ms = 0;
+  uint32_t launches = 0;
+  HIP_TRY(hipEventRecord(ctx->ev0, st));
+  if ((rc = run_preview(ctx, req, sc, tr, sp, pp, ap, num_pixels, chunk, &trace_ms, &shade_ms, &launches))) return rc;
+  hipLaunchKernelGGL(k_cpart_reduce, dim3(CNT_N), dim3(256), 0, st, ctx->d_cpart, cpart_rows, ctx->d_counters);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(ctx->ev1, st));
+  if ((rc = apply_post(ctx, req, out_dev))) return rc;
+  HIP_TRY(hipEventSynchronize(ctx->ev1));
+  HIP_TRY(hipEventElapsedTime(&total_ms, ctx->ev0, ctx->ev1));
+  unsigned long long cnt[CNT_N];
+  uint32_t guard = 0;
+  HIP_TRY(hipMemcpy(cnt, ctx->d_counters, sizeof(cnt), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&guard, misc(ctx, 1), sizeof(guard), hipMemcpyDeviceToHost));
+  izpi_render_stats& s = ctx->last;
+  memset(&s, 0, sizeof(s));
+  s.rays = cnt[CNT_RAYS]; s.node_visits = cnt[CNT_NODES]; s.tri_tests = cnt[CNT_TRI]; s.sph_tests = cnt[CNT_SPH];
+  s.samples = (uint64_t)num_pixels * req->spp;
+  s.kernel_ms = trace_ms; s.shade_ms = shade_ms; s.total_ms = total_ms; s.launches = launches;
+  s.node_steps = cnt[CNT_NSTEP]; s.prim_steps = cnt[CNT_PSTEP]; s.leaf_shortcuts = cnt[CNT_SHORT];
+  s.workspace_bytes = workspace_bytes(ctx);
+  s.scene_bytes = ctx->scene_bytes;
+  s.slots = slots; s.chunk_spp = chunk; s.alloc_ms = alloc_ms;
+  if (guard) { ctx->err = "device guard: traversal stack overflow"; return IZPI_ERR_DEVICE; }
+  return IZPI_OK;
+}
+
 int render_body(izpi_ctx* ctx, const izpi_render_req* req, double* out_dev);
 // One render on one context. The progress counters (izpi_gpu_progress) start at 0/0 before
 // any check and read done == total on every return, failed calls included.
@@ -451,9 +578,11 @@ int render_body(izpi_ctx* ctx, const izpi_render_req* req, double* out_dev) {
   if (!ctx->have_scene) { ctx->err = "render before izpi_gpu_upload_scene"; return IZPI_ERR_NO_SCENE; }
   if (!req || req->width == 0 || req->height == 0 || req->spp == 0) { ctx->err = "invalid render request"; return IZPI_ERR_INVALID; }
   if (req->abi_version > IZPI_ABI_VERSION) { ctx->err = "render request from a newer ABI"; return IZPI_ERR_INVALID; }
-  if (req->sampler != IZPI_SAMPLER_COLOUR && req->sampler != IZPI_SAMPLER_SPECTRAL) { ctx->err = "unsupported sampler"; return IZPI_ERR_UNSUPPORTED; }
+  const bool preview = preview_sampler(req->sampler);
+  if (req->sampler != IZPI_SAMPLER_COLOUR && req->sampler != IZPI_SAMPLER_SPECTRAL && !preview) { ctx->err = "unsupported sampler"; return IZPI_ERR_UNSUPPORTED; }
   // (a request of ABI 1 or 2 ends at `tuning`: accumulation is not read)
-  const uint32_t acc = req->abi_version >= 3 ? req->accumulation : (uint32_t)IZPI_ACC_RECURSIVE;
+  // (the preview samplers ignore it, as they ignore max_depth)
+  const uint32_t acc = preview ? (uint32_t)IZPI_ACC_RECURSIVE : req->abi_version >= 3 ? req->accumulation : (uint32_t)IZPI_ACC_RECURSIVE;
   if (acc != IZPI_ACC_RECURSIVE && acc != IZPI_ACC_FORWARD) { ctx->err = "unknown accumulation mode"; return IZPI_ERR_INVALID; }
   const bool fwd = acc == IZPI_ACC_FORWARD;
   if (req->post != IZPI_POST_NONE &&
@@ -462,11 +591,18 @@ int render_body(izpi_ctx* ctx, const izpi_render_req* req, double* out_dev) {
     ctx->err = "post-processing needs a whole-frame IZPI_OUT_CANVAS request";
     return IZPI_ERR_INVALID;
   }
-  if (req->sampler == IZPI_SAMPLER_COLOUR ? !ctx->mat_ok_rgb : !ctx->mat_ok_spectral) {
+  if (preview && (req->post & IZPI_POST_SPECTRAL)) {
+    ctx->err = "IZPI_POST_SPECTRAL needs the Spectral sampler's XYZ canvas";
+    return IZPI_ERR_INVALID;
+  }
+  // Normal and WireFrame read no material texture but the normal maps; Albedo reads Colour's
+  if (req->sampler == IZPI_SAMPLER_COLOUR || req->sampler == IZPI_SAMPLER_ALBEDO ? !ctx->mat_ok_rgb
+      : req->sampler == IZPI_SAMPLER_SPECTRAL                                     ? !ctx->mat_ok_spectral
+                                                                                  : false) {
     ctx->err = "a material lacks the textures this sampler reads";
     return IZPI_ERR_INVALID;
   }
-  if (ctx->sc.num_lights == 0) { ctx->err = "scene has no lights (HitableSlice.PDFValue divides by zero)"; return IZPI_ERR_INVALID; }
+  if (!preview && ctx->sc.num_lights == 0) { ctx->err = "scene has no lights (HitableSlice.PDFValue divides by zero)"; return IZPI_ERR_INVALID; }
   std::vector<uint32_t> tiles;
   int rc = request_tiles(ctx, req, tiles);
   if (rc) return rc;
@@ -488,6 +624,7 @@ int render_body(izpi_ctx* ctx, const izpi_render_req* req, double* out_dev) {
   int trc = make_tracer(ctx, tu, !ctx->sc.tri_only || ctx->any_uv, &tr);
   if (trc) return trc;
   const double t_tracer = host_ms();
+  if (preview) return preview_body(ctx, req, sc, tr, tu, tiles, tw, th, num_pixels, out_dev);
   // Sizing against the HBM this context may use: what is free plus the render buffers it
   // holds and would release (a later frame reuses them, so every frame of a renderer sizes
   // alike), shared evenly by the contexts of one process on this device.
@@ -1149,6 +1286,19 @@ int izpi_gpu_upload_scene(izpi_ctx* ctx, const izpi_scene_desc* d) {
   UP(leaves.data(), leaves.size(), &dl);
   UP(prims.data(), prims.size(), &dp);
   UP(shade.data(), shade.size(), &dsh);
+  {  // the triangles' v1, v2 in leaf order (Triangle.HitEdge's sides: the WireFrame sampler)
+    std::vector<GTriVerts> tv(std::max<uint32_t>(1, d->num_prims));
+    memset(tv.data(), 0, tv.size() * sizeof(GTriVerts));
+    for (uint32_t k = 0; k < d->num_prims; k++) {
+      const uint32_t r = d->prim_ref[k];
+      if (IZPI_PRIM_KIND(r) != IZPI_PRIM_TRIANGLE) continue;
+      memcpy(tv[k].v1, d->tri_v1 + 3 * (size_t)IZPI_PRIM_INDEX(r), 24);
+      memcpy(tv[k].v2, d->tri_v2 + 3 * (size_t)IZPI_PRIM_INDEX(r), 24);
+    }
+    GTriVerts* dtv;
+    UP(tv.data(), tv.size(), &dtv);
+    ctx->d_triverts = dtv;
+  }
   for (uint32_t i = 0; i < d->num_materials; i++)
     if (d->materials[i].kind == IZPI_MAT_PBR && d->materials[i].normal_tex >= 0 && nt && (!d->tri_tangent || !d->tri_bitangent)) {
       ctx->err = "a PBR normal map needs the triangles' tangents and bitangents";
@@ -1312,6 +1462,7 @@ int izpi_gpu_upload_scene(izpi_ctx* ctx, const izpi_scene_desc* d) {
   }
   ctx->have_scene = true;
   ctx->sizing_valid = false;  // per-slot sizes depend on the scene
+  ctx->pv_sizing_valid = false;
   ctx->num_textures = d->num_textures;
   ctx->num_materials = d->num_materials;
   ctx->num_spd = d->num_spd;
@@ -1326,6 +1477,7 @@ int izpi_gpu_upload_scene(izpi_ctx* ctx, const izpi_scene_desc* d) {
     if (!rc && ctx->mat_ok_rgb) rc = prepare_sampler<IZPI_SAMPLER_COLOUR, false>(ctx, compact);
     if (!rc && ctx->mat_ok_spectral) rc = prepare_sampler<IZPI_SAMPLER_SPECTRAL, true>(ctx, false);
     if (!rc && ctx->mat_ok_spectral) rc = prepare_sampler<IZPI_SAMPLER_SPECTRAL, false>(ctx, false);
+    if (!rc) rc = prepare_preview(ctx);
     if (rc) return rc;
   }
   return IZPI_OK;

@@ -1,6 +1,7 @@
-// izpi_kern.h — internal header of libizpi_gpu.so, shared by its three HIP translation units:
+// izpi_kern.h — internal header of libizpi_gpu.so, shared by its HIP translation units:
 //   trace.hip     k_trace2 (BVH4.Hit) and its instance selection;
 //   shade.hip     k_start / k_shade / k_tail / k_accumulate and the wavefront pass loop;
+//   preview.hip   k_preview_start / k_preview: the Normal, Albedo and WireFrame samplers;
 //   izpi_gpu.hip  the C ABI, the context, scene upload, workspace sizing, multi-GPU.
 // Device helpers (textures, spectra, the wavefront state, hit records, lights, materials,
 // the shading records) and the host context live here. Not part of the ABI.
@@ -1461,6 +1462,9 @@ struct izpi_ctx {
     uint32_t chunk, slots, pool_blocks, pool_div;
   } sizing{};
   bool sizing_valid = false;
+  Sizing pv_sizing{};            // the same for the preview samplers' workspace (preview_body)
+  bool pv_sizing_valid = false;
+  const GTriVerts* d_triverts = nullptr;  // [num_prims], leaf order: the triangles' v1, v2 (WireFrame's edge test); a scene allocation
   DevScene sc{};
   uint32_t stack_needed = 0;
   uint32_t num_prims = 0;
@@ -1567,6 +1571,27 @@ int run_sampler(izpi_ctx* ctx, const izpi_render_req* req, const DevScene& sc, c
 // for the uploaded scene (izpi_gpu_upload_scene, ahead of the first frame).
 template <int SAMPLER, bool FWD>
 int prepare_sampler(izpi_ctx* ctx, bool compact);
+// preview.hip: the Normal, Albedo and WireFrame samplers (sampler/normal.go, albedo.go,
+// wireframe.go): one primary ray per sample, no path state. The request's units run in
+// batches of `slots`: k_preview_start writes the batch's camera rays into `buf` (start_path),
+// k_trace2 traces them in place, k_preview writes each sample's result; WireFrame re-enqueues
+// every hit with tMax = t + 2^-52 in buf.tminmax and traces and tests the batch once more
+// (HitableSlice.HitEdge's two traversals). k_accumulate folds each chunk as for Colour.
+struct PreviewParams {
+  WaveBuf buf;            // one side of state: ray, kind, time, hit (+ (u, v)); no path state
+  double2* tminmax;       // WireFrame: (tMin, tMax) of the second traversal, per entry; else null
+  const GTriVerts* verts; // izpi_ctx::d_triverts
+  double ink[3];          // WireFrame: the edge colour (the paper is ShadeParams::background)
+  uint32_t slots;         // entries of buf
+};
+int run_preview(izpi_ctx* ctx, const izpi_render_req* req, const DevScene& sc, const Tracer& tr, ShadeParams& sp,
+                const PreviewParams& pp, AccumParams& ap, uint32_t num_pixels, uint32_t chunk, float* trace_ms,
+                float* shade_ms, uint32_t* launches);
+// preview.hip: load the code of the preview kernels (izpi_gpu_upload_scene)
+int prepare_preview(izpi_ctx* ctx);
+inline bool preview_sampler(uint32_t s) {
+  return s == IZPI_SAMPLER_NORMAL || s == IZPI_SAMPLER_ALBEDO || s == IZPI_SAMPLER_WIREFRAME;
+}
 // Diagnostics (IZPI_TUNE_PASS_LOG): host milliseconds on a process-wide steady clock.
 inline double diag_clock_ms() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();

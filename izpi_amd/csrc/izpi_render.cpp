@@ -6,6 +6,7 @@
 //               [--samples 512] [--depth 50] [--bvh gpu|reference] [--quantized] [--png-pipeline]
 //               [--accumulation forward|recursive] [--out image.pfm] [--raw canvas.f64]
 //               [--device 0 | --gpus N] [--seed 12345]
+//               [--sampler colour|normal|wireframe|albedo|spectral] [--ink r,g,b]
 //
 // Defaults are the Go shim's: the GPU-built tree and the forward accumulation
 // (IZPI_ACC_FORWARD; --accumulation recursive is bit-identical to the CPU oracle).
@@ -13,7 +14,8 @@
 //
 // The scene file is read as leader.go:54-75 does (.pbtxt text, .izpi binary); a SPECTRAL
 // scene renders with the spectral sampler and Render's post-processing (leader.go:77-81,
-// renderer.go:215-219). --obj streams a Wavefront mesh into the scene with the
+// renderer.go:215-219); --sampler picks another of render.New's five (sampler.go:22-28;
+// wireframe draws edges in --ink, default black, on a black paper). --obj streams a Wavefront mesh into the scene with the
 // transforms of scenes/spectral.go:644-646. The canvas is written as a PFM (float32 RGB,
 // bottom row first) and/or the raw W*H*4 float64 canvas.
 #include <stdint.h>
@@ -56,7 +58,8 @@ constexpr double kMinus60Deg = -0x1.0c152382d7366p+0;  // == -ingest.go_radians(
 }  // namespace
 
 int main(int argc, char** argv) {
-  std::string scene_path, obj_path, obj_material = "White", out_pfm, out_raw, bvh = "gpu", acc = "forward";
+  std::string scene_path, obj_path, obj_material = "White", out_pfm, out_raw, bvh = "gpu", acc = "forward", sampler_name;
+  double ink[3] = {0.0, 0.0, 0.0};
   bool quantized = false;
   uint32_t W = 1024, H = 1024, spp = 16, depth = 50, device = 0, gpus = 1;
   uint64_t seed = 12345;
@@ -80,6 +83,8 @@ int main(int argc, char** argv) {
     else if (a == "--device") device = (uint32_t)atoi(val().c_str());
     else if (a == "--gpus") gpus = (uint32_t)atoi(val().c_str());
     else if (a == "--seed") seed = strtoull(val().c_str(), nullptr, 10);
+    else if (a == "--sampler") sampler_name = val();
+    else if (a == "--ink") { if (sscanf(val().c_str(), "%lf,%lf,%lf", &ink[0], &ink[1], &ink[2]) != 3) die("--ink takes r,g,b"); }
     else die("unknown option " + a);
   }
   if (scene_path.empty()) die("--scene is required");
@@ -118,7 +123,16 @@ int main(int argc, char** argv) {
     }
     izpi_obj_free(mesh);
   }
-  const bool spectral = info.colour_representation == IZPI_COLOUR_SPECTRAL;
+  // the sampler: the scene file's colour representation (leader.go:77-81) unless --sampler names one (sampler.go:22-28)
+  uint32_t sampler = info.colour_representation == IZPI_COLOUR_SPECTRAL ? IZPI_SAMPLER_SPECTRAL : IZPI_SAMPLER_COLOUR;
+  if (sampler_name == "colour") sampler = IZPI_SAMPLER_COLOUR;
+  else if (sampler_name == "normal") sampler = IZPI_SAMPLER_NORMAL;
+  else if (sampler_name == "wireframe") sampler = IZPI_SAMPLER_WIREFRAME;
+  else if (sampler_name == "albedo") sampler = IZPI_SAMPLER_ALBEDO;
+  else if (sampler_name == "spectral") sampler = IZPI_SAMPLER_SPECTRAL;
+  else if (!sampler_name.empty()) die("--sampler must be colour, normal, wireframe, albedo or spectral");
+  else sampler_name = sampler == IZPI_SAMPLER_SPECTRAL ? "spectral" : "colour";
+  const bool spectral = sampler == IZPI_SAMPLER_SPECTRAL;
   // ---- transport.ToScene, BVH, upload
   auto t0 = std::chrono::steady_clock::now();
   const izpi_scene_input* in = nullptr;
@@ -162,7 +176,8 @@ int main(int argc, char** argv) {
   memset(&req, 0, sizeof req);
   req.abi_version = IZPI_ABI_VERSION;
   req.width = W; req.height = H; req.spp = spp; req.max_depth = depth;
-  req.sampler = spectral ? IZPI_SAMPLER_SPECTRAL : IZPI_SAMPLER_COLOUR;
+  req.sampler = sampler;
+  for (int k = 0; k < 3; k++) req.ink[k] = ink[k];
   req.out_layout = IZPI_OUT_CANVAS;
   req.seed = seed;
   req.exposure = izpi_host_scene_desc(host)->camera.exposure;
@@ -181,7 +196,7 @@ int main(int argc, char** argv) {
   const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
   printf("{\"scene\": \"%s\", \"width\": %u, \"height\": %u, \"spp\": %u, \"bvh\": \"%s\", \"quantized\": %d, \"accumulation\": \"%s\", \"sampler\": \"%s\", \"gpus\": %u, "
          "\"setup_s\": %.3f, \"render_s\": %.4f, \"msamples_per_s\": %.2f, \"rays\": %llu, \"node_visits\": %llu}\n",
-         scene_path.c_str(), W, H, spp, bvh.c_str(), bvh == "gpu" && quantized ? 1 : 0, acc.c_str(), spectral ? "spectral" : "colour", gpus > 1 ? gpus : 1u, setup_s, secs,
+         scene_path.c_str(), W, H, spp, bvh.c_str(), bvh == "gpu" && quantized ? 1 : 0, acc.c_str(), sampler_name.c_str(), gpus > 1 ? gpus : 1u, setup_s, secs,
          (double)W * H * spp / secs / 1e6, (unsigned long long)st.rays, (unsigned long long)st.node_visits);
   // ---- outputs
   if (!out_raw.empty()) {

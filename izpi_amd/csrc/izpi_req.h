@@ -20,10 +20,13 @@ inline izpi_render_tuning tuning_of(const izpi_render_req* req) {
 
 // The library's own copy of the caller's request (req != NULL). A request of ABI 1 or 2
 // (abi_version below 3) ends at `tuning`: only that prefix is the caller's to read, and
-// the later fields are zero (accumulation = IZPI_ACC_RECURSIVE).
+// the later fields are zero (accumulation = IZPI_ACC_RECURSIVE). A request of ABI 3 ends at
+// `pad_req`: it is read up to `ink`, which stays zero (black).
 inline izpi_render_req request_copy(const izpi_render_req* req) {
   izpi_render_req q;
   memset(&q, 0, sizeof q);
-  memcpy(&q, req, req->abi_version < 3 ? offsetof(izpi_render_req, accumulation) : sizeof q);
+  memcpy(&q, req, req->abi_version < 3    ? offsetof(izpi_render_req, accumulation)
+                  : req->abi_version == 3 ? offsetof(izpi_render_req, ink)
+                                          : sizeof q);
   return q;
 }

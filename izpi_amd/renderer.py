@@ -63,13 +63,15 @@ def build_bvh4(ctx, boxes, leaf_max=4, method=None):
 
 
 def make_request(width, height, spp, max_depth, sampler, background, seed, exposure, bg_spd=None, tiles=None,
-                 layout=N.OUT_CANVAS, post=N.POST_NONE, tuning=None, accumulation=N.ACC_RECURSIVE):
+                 layout=N.OUT_CANVAS, post=N.POST_NONE, tuning=None, accumulation=N.ACC_RECURSIVE, ink=(0.0, 0.0, 0.0)):
     """izpi_render_req for Render (the arrays it points to are kept alive on `req._keep`).
     tuning: an N.RenderTuning (launch settings; None = the library's defaults).
-    accumulation: N.ACC_RECURSIVE (bitwise against the oracle's recursion) or N.ACC_FORWARD."""
+    accumulation: N.ACC_RECURSIVE (bitwise against the oracle's recursion) or N.ACC_FORWARD.
+    ink: the WireFrame sampler's edge colour (its paper is `background`)."""
     req = N.RenderReq()
     req.abi_version = N.IZPI_ABI_VERSION
     req.accumulation = accumulation
+    req.ink[:] = ink
     req.post = post
     req.exposure = exposure
     req.width, req.height = width, height
@@ -110,8 +112,10 @@ def common_tiles(width, height):
 class GPURenderer:
     def __init__(self, scene, width, height, spp, max_depth=50, sampler=N.SAMPLER_COLOUR, background=(0.0, 0.0, 0.0),
                  spectral_background=None, device=0, seed=12345, bvh_seed=12345, host_scene=None, bvh="reference",
-                 bvh_leaf_max=None, tuning=None, accumulation=N.ACC_RECURSIVE, bvh_quantized=False):
-        """bvh="reference": hitable.NewBVH4's tree, rebuilt bit for bit on the host (the
+                 bvh_leaf_max=None, tuning=None, accumulation=N.ACC_RECURSIVE, bvh_quantized=False, ink=(0.0, 0.0, 0.0)):
+        """sampler: any of render.New's five (N.SAMPLER_*, by name in izpi_amd.SAMPLERS); the
+        WireFrame sampler draws edges in `ink` on a paper of `background`.
+        bvh="reference": hitable.NewBVH4's tree, rebuilt bit for bit on the host (the
         parity default); bvh="gpu": the GPU linear BVH4 builder (izpi_gpu_build_bvh4),
         same node format, different topology. tuning: an
         N.RenderTuning for every request (None = library defaults). accumulation: how a
@@ -127,6 +131,7 @@ class GPURenderer:
         self.width, self.height, self.spp, self.max_depth = int(width), int(height), int(spp), int(max_depth)
         self.sampler = int(sampler)
         self.background = tuple(float(b) for b in background)
+        self.ink = tuple(float(b) for b in ink)
         self.seed = int(seed)
         self.device = int(device)
         # leader mode: aspect = W/H overrides the scene camera (transport.go aspectOverride)
@@ -180,7 +185,7 @@ class GPURenderer:
     def request(self, tiles=None, layout=N.OUT_CANVAS, spp=None, post=N.POST_NONE):
         return make_request(self.width, self.height, self.spp if spp is None else int(spp), self.max_depth,
                             self.sampler, self.background, self.seed, self.exposure, (self._bg_wl, self._bg_val),
-                            tiles, layout, post, self.tuning, self.accumulation)
+                            tiles, layout, post, self.tuning, self.accumulation, self.ink)
 
     # --------------------------------------------------------------- render
     @property
@@ -310,9 +315,10 @@ class MultiGPURenderer:
 
     def __init__(self, scene, width, height, spp, devices, max_depth=50, sampler=N.SAMPLER_COLOUR,
                  background=(0.0, 0.0, 0.0), spectral_background=None, seed=12345, bvh_seed=12345, bvh="gpu",
-                 bvh_leaf_max=None, tuning=None, accumulation=N.ACC_RECURSIVE, bvh_quantized=False):
+                 bvh_leaf_max=None, tuning=None, accumulation=N.ACC_RECURSIVE, bvh_quantized=False, ink=(0.0, 0.0, 0.0)):
         self.tuning = tuning
         self.accumulation = int(accumulation)
+        self.ink = tuple(float(b) for b in ink)
         self.bvh_quantized = bool(bvh_quantized)
         if bvh not in ("reference", "gpu"):
             raise ValueError("bvh must be 'reference' or 'gpu'")
@@ -359,7 +365,7 @@ class MultiGPURenderer:
         list of per-device stats."""
         req = make_request(self.width, self.height, self.spp, self.max_depth, self.sampler, self.background,
                            self.seed, self.exposure, self._bg, None, N.OUT_CANVAS, post, self.tuning,
-                           self.accumulation)
+                           self.accumulation, self.ink)
         G = len(self.devices)
         st = (N.RenderStats * G)()
         if to_host and canvas is None:
@@ -373,7 +379,7 @@ class MultiGPURenderer:
         """izpi_gpu_multi_prepare: every device's workspace for its share, ahead of the first frame."""
         req = make_request(self.width, self.height, self.spp, self.max_depth, self.sampler, self.background,
                            self.seed, self.exposure, self._bg, None, N.OUT_CANVAS, post, self.tuning,
-                           self.accumulation)
+                           self.accumulation, self.ink)
         self._check(N.lib().izpi_gpu_multi_prepare(self.m, C.byref(req)), "izpi_gpu_multi_prepare")
 
     def close(self):
