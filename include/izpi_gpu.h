@@ -143,8 +143,10 @@ enum {
   IZPI_TUNE_NO_RAY_LDS = 128,     /* triangle-only scenes without (u, v) reads: primitive tests re-read the ray from global memory */
   IZPI_TUNE_NO_PRIM_LDS = 256,    /* small scenes: shading reads the primitives' records from global memory, not the per-block LDS copy */
   IZPI_TUNE_NO_PLACE_PICK = 512,  /* ignored since ABI 3 (the record arrays' page pick of ABI 2 is gone) */
-  IZPI_TUNE_NO_QNODES = 1024      /* a quantised scene (IZPI_SCENE_QUANTIZED_BVH): k_trace2 reads the decoded 128-B nodes
+  IZPI_TUNE_NO_QNODES = 1024,     /* a quantised scene (IZPI_SCENE_QUANTIZED_BVH): k_trace2 reads the decoded 128-B nodes
                                      instead of the 64-B quantised ones (the same boxes) */
+  IZPI_TUNE_NO_SHADE_STAGE = 2048 /* forward Colour renders: k_shade reserves its output entries every block-iteration
+                                     instead of every other one with the first's entries staged in LDS */
 };
 
 typedef struct izpi_render_req {

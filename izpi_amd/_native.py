@@ -95,6 +95,7 @@ TUNE_NO_LDS_BVH = 64
 TUNE_NO_RAY_LDS = 128
 TUNE_NO_PRIM_LDS = 256
 TUNE_NO_QNODES = 1024
+TUNE_NO_SHADE_STAGE = 2048
 
 
 def tuning(**kw):

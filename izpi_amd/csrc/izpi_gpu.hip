@@ -795,6 +795,14 @@ int render_body(izpi_ctx* ctx, const izpi_render_req* req, double* out_dev) {
               ctx->num_textures <= TEX_LDS && ctx->num_spd <= SPD_LDS && nbg <= BG_LDS;
   sp.prims_staged = sc.num_prims <= PR_LDS && !(tuning_of(req).flags & IZPI_TUNE_NO_PRIM_LDS);
   if (sp.staged && (req->sampler == IZPI_SAMPLER_SPECTRAL || ctx->num_spd)) sp.staged = 2;  // + the Spectral tables
+  // A forward Colour render of a Lambert / light scene (C1, C2) that could run k_shade's staged
+  // form but for its primitives in LDS (the output stage lies behind the Colour tables, where
+  // they would) leaves them in global memory: its hits read their 32-B GShade only, and C2's
+  // shading at 256 spp measured 35.0-35.3 ms with the primitives in LDS, 34.3-34.4 without and
+  // 30.3-30.4 without them in the staged form (run_chunks; profiles/r7b/ab_stage_c2.jsonl).
+  if (fwd && req->sampler == IZPI_SAMPLER_COLOUR && ctx->matset == 0 && sp.staged == 1 && !rec_pool && !need_time && !need_cold &&
+      !(tuning_of(req).flags & IZPI_TUNE_NO_SHADE_STAGE))
+    sp.prims_staged = 0;
   // k_shade / k_tail's LDS arena: the prefix of lds_off's layout that this render stages
   sc.lds_bytes = sp.prims_staged ? lds_off::END : sp.staged == 2 ? lds_off::SPECTRAL_END : sp.staged ? lds_off::COLOUR_END : 0;
   sp.pool = rec_pool ? ctx->d_pool : nullptr; sp.pool_ring = rec_pool ? ctx->d_ring : nullptr;

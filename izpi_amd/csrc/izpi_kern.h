@@ -166,6 +166,15 @@ constexpr uint32_t GS = SPECTRAL_END;                             // GShade [PR_
 constexpr uint32_t TT = GS + al(PR_LDS * sizeof(GShade));         // GTriTex [PR_LDS]
 constexpr uint32_t GP = TT + al(PR_LDS * sizeof(GTriTex));        // GPrim [PR_LDS]
 constexpr uint32_t END = GP + al(PR_LDS * sizeof(GPrim));
+// The forward Colour k_shade's output stage (shade.h: stage_put), behind the Colour tables of
+// a render that stages nothing else: one block-iteration's continuing entries, as planes that
+// mirror the arrays store_entry<COLOUR, forward> writes (92 B per entry, 23 KB).
+constexpr uint32_t STG_RAY = COLOUR_END;                                  // double2 [3][SHADE_THREADS]: (o.x, o.y), (o.z, d.x), (d.y, d.z)
+constexpr uint32_t STG_THR = STG_RAY + 3 * SHADE_THREADS * 16;            // double [3][SHADE_THREADS]: the throughput planes
+constexpr uint32_t STG_PATH = STG_THR + 3 * SHADE_THREADS * 8;            // PathHot [SHADE_THREADS]
+constexpr uint32_t STG_KIND = STG_PATH + SHADE_THREADS * 16;              // kind word [SHADE_THREADS]
+constexpr uint32_t STG_END = STG_KIND + SHADE_THREADS * 4;
+constexpr uint32_t STG_BYTES = STG_END - COLOUR_END;
 }  // namespace lds_off
 IZPI_DEV char* lds_arena() {
   extern __shared__ __attribute__((aligned(16))) char izpi_lds_arena[];

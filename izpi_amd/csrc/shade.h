@@ -159,6 +159,99 @@ IZPI_DEV void block_reserve2(const ShadeParams& sp, uint32_t* out_count, bool pu
   pos = put ? s_pbase[b] + pr : (has_entry ? s_pbase[b] + s_nput[b] + ur : 0xFFFFFFFFu);
 }
 
+// ---- the forward Colour k_shade's staged form (k_shade<..., STAGE = true>)
+// One word serves ~88 returning atomics per microsecond chip-wide, and block_reserve2's one
+// per block-iteration on *out_count (5.75 M per C3 frame) had become the floor of forward
+// shading. Which entries a block gets does not change the image, so every other iteration
+// (phase 0) keeps its continuing entries in LDS, ranked within the block (stage_put: one
+// barrier, no atomic), and the next one (phase 1) reserves for both with one atomic
+// (block_reserve_fwd) and copies the staged entries out in front of its own (stage_flush).
+// The stage is lds_off::STG_*: planes that mirror the arrays store_entry writes for a
+// forward Colour render without ray times, overflow blocks or cold records.
+typedef double stg_d2 __attribute__((ext_vector_type(2)));
+typedef uint32_t stg_u4 __attribute__((ext_vector_type(4)));
+#define IZPI_LDS3 __attribute__((address_space(3)))
+IZPI_DEV IZPI_LDS3 stg_d2* stg_ray() { return (IZPI_LDS3 stg_d2*)(lds_arena() + lds_off::STG_RAY); }
+IZPI_DEV IZPI_LDS3 double* stg_thr() { return (IZPI_LDS3 double*)(lds_arena() + lds_off::STG_THR); }
+IZPI_DEV IZPI_LDS3 stg_u4* stg_path() { return (IZPI_LDS3 stg_u4*)(lds_arena() + lds_off::STG_PATH); }
+IZPI_DEV IZPI_LDS3 uint32_t* stg_kind() { return (IZPI_LDS3 uint32_t*)(lds_arena() + lds_off::STG_KIND); }
+// Phase 0: the `put` lanes' entries go to the stage at their block-local rank; returns their
+// number (the same in every thread). The block's next use of s_n is two iterations on, behind
+// the barriers of block_reserve_fwd.
+IZPI_DEV uint32_t stage_put(bool put, const PathSt& P, const RayRec& R) {
+  __shared__ uint32_t s_n[SHADE_WAVES];
+  const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const uint64_t mp = __ballot(put);
+  if (lane == 0) s_n[w] = (uint32_t)__popcll(mp);
+  SCLK_T(rb0);
+  __syncthreads();
+  SCLK_ADD(SCLK_RB1, rb0);
+  uint32_t r = (uint32_t)__popcll(mp & ((1ull << lane) - 1)), n = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < SHADE_WAVES; k++) {
+    r += k < w ? s_n[k] : 0u;
+    n += s_n[k];
+  }
+  if (put) {
+    stg_ray()[r] = stg_d2{R.o[0], R.o[1]};
+    stg_ray()[SHADE_THREADS + r] = stg_d2{R.o[2], R.d[0]};
+    stg_ray()[2 * SHADE_THREADS + r] = stg_d2{R.d[1], R.d[2]};
+    stg_thr()[r] = P.thr[0];
+    stg_thr()[SHADE_THREADS + r] = P.thr[1];
+    stg_thr()[2 * SHADE_THREADS + r] = P.thr[2];
+    stg_path()[r] = stg_u4{P.rng, P.depth | P.zf << 16, P.unit, P.rslot};
+    stg_kind()[r] = R.kind;
+  }
+  return n;
+}
+// Phase 1's reservation (block_reserve2 without units): `staged` + the block's `put` lanes
+// entries of *out_count in one atomic, none when that is nothing. `base` is the first of
+// them, `rank` the lane's rank among the `put` lanes. Two calls are always a stage_put
+// (a barrier) apart, so one set of LDS words serves.
+IZPI_DEV void block_reserve_fwd(uint32_t* out_count, bool put, uint32_t staged, uint32_t& base, uint32_t& rank) {
+  __shared__ uint32_t s_p[SHADE_WAVES], s_base;
+  const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const uint64_t mp = __ballot(put);
+  if (lane == 0) s_p[w] = (uint32_t)__popcll(mp);
+  SCLK_T(rb0);
+  __syncthreads();
+  SCLK_ADD(SCLK_RB1, rb0);
+  SCLK_T(rb1);
+  if (threadIdx.x == 0) {
+    uint32_t ne = staged;
+#pragma unroll
+    for (uint32_t k = 0; k < SHADE_WAVES; k++) ne += s_p[k];
+    s_base = ne ? atomicAdd(out_count, ne) : 0u;
+    SCLK_VMWAIT();
+    SCLK_ADD(SCLK_RATOM, rb1);
+  }
+  __syncthreads();
+  SCLK_ADD(SCLK_RB2, rb1);
+  rank = (uint32_t)__popcll(mp & ((1ull << lane) - 1));
+  for (uint32_t k = 0; k < w; k++) rank += s_p[k];
+  base = s_base;
+}
+// Thread t < n copies staged entry t to entry base + t of `out` (after block_reserve_fwd's
+// second barrier): consecutive positions, 16 B or 8 B per lane and array.
+IZPI_DEV void stage_flush(const WaveBuf& out, uint32_t base, uint32_t n) {
+  const uint32_t t = threadIdx.x;
+  if (t >= n) return;
+  const uint32_t pos = base + t;
+  const stg_d2 r0 = stg_ray()[t], r1 = stg_ray()[SHADE_THREADS + t], r2 = stg_ray()[2 * SHADE_THREADS + t];
+  const double t0 = stg_thr()[t], t1 = stg_thr()[SHADE_THREADS + t], t2 = stg_thr()[2 * SHADE_THREADS + t];
+  const stg_u4 ph = stg_path()[t];
+  const uint32_t kind = stg_kind()[t];
+  sst(out.thr + pos, t0);
+  sst(out.thr + out.tplane + pos, t1);
+  sst(out.thr + 2 * (size_t)out.tplane + pos, t2);
+  double2* r = reinterpret_cast<double2*>(out.ray + pos);
+  sst(r, make_double2(r0.x, r0.y));
+  sst(r + 1, make_double2(r1.x, r1.y));
+  sst(r + 2, make_double2(r2.x, r2.y));
+  sst(out.kind + pos, kind);
+  sst(out.path + pos, PathHot{ph.x, ph.y, ph.z, ph.w});
+}
+
 // A lane whose path finished got `unit` and entry `pos` (block_reserve2): start the
 // unit's path in the finished path's record slot and store it; when its sample completes
 // without a ray, take further units one at a time (rare), and leave a dead entry when
@@ -551,12 +644,21 @@ constexpr int SHADE_WPE = 3;
 // Forward mode: a finished path frees its entry and starts nothing; k_refill starts the new
 // units after the pass (see there). The recursion's new paths take over the finished
 // paths' record slots, here.
-template <int SAMPLER, int MATSET, bool FWD>
+// STAGE: the staged form of the forward Colour instances (stage_put), chosen per render by
+// run_chunks; its output stage lies behind the Colour tables in the LDS arena. MATSET_BASIC
+// and MATSET_SURF have one (165 and 168 VGPRs, no spill); MATSET_FULL's spilled 18 VGPRs
+// and is not compiled (its dielectric scenes carry cold records, which the stage lacks).
+constexpr bool shade_can_stage(int sampler, int matset, bool fwd) {
+  return fwd && sampler == IZPI_SAMPLER_COLOUR && matset != MATSET_FULL;
+}
+template <int SAMPLER, int MATSET, bool FWD, bool STAGE = false>
 __global__ void __launch_bounds__(SHADE_THREADS) __attribute__((amdgpu_waves_per_eu(SHADE_WPE)))
 k_shade(const DevScene sc, const ShadeParams sp, const WaveParams wp) {
+  static_assert(!STAGE || shade_can_stage(SAMPLER, MATSET, FWD), "no staged form of this instance");
   constexpr bool DREF = FWD;
   shade_stage(sc, sp);
   uint32_t parity = 0;  // block_reserve2 LDS buffer set
+  uint32_t st_phase = 0, st_n = 0;  // (STAGE) 1: the stage holds the st_n entries of the iteration before
   const uint32_t n = *wp.in_count;
   // (forward mode) `in`'s camera entries: their path state is computed, not loaded
   const uint32_t cam_b = FWD && wp.cam ? wp.cam[0] : 0u, cam_u = FWD && wp.cam ? wp.cam[1] : 0u,
@@ -619,13 +721,25 @@ k_shade(const DevScene sc, const ShadeParams sp, const WaveParams wp) {
 #endif
     // one reservation phase: output entries for continuing and parked paths, new units
     // (and their entries) for finished ones
-    uint32_t unit, pos, frank, ftotal;
-    block_reserve2<COLOUR_DEFER>(sp, wp.out_count, push || parked, done && !DREF, unit, pos, parity, exhausted, queued, frank,
-                                 ftotal);
-    if (queued) fin_queue<SAMPLER>(fq, fq_n + frank, P, R);  // (before refill_one reuses P)
-    fq_n += ftotal;
-    if (push) store_entry<SAMPLER, FWD>(wp.out, pos, P, R);
-    if (parked) copy_entry(wp.in, i, wp.out, pos);
+    uint32_t unit = 0xFFFFFFFFu, pos = 0xFFFFFFFFu, frank = 0, ftotal = 0;
+    if constexpr (STAGE) {  // (no pool: nothing parks; no unit or unwinding job is taken here)
+      if (st_phase == 0) {  // block-uniform
+        st_n = stage_put(push, P, R);
+      } else {
+        uint32_t rbase, rank;
+        block_reserve_fwd(wp.out_count, push, st_n, rbase, rank);
+        if (push) store_entry<SAMPLER, FWD>(wp.out, rbase + st_n + rank, P, R);
+        stage_flush(wp.out, rbase, st_n);
+      }
+      st_phase ^= 1u;
+    } else {
+      block_reserve2<COLOUR_DEFER>(sp, wp.out_count, push || parked, done && !DREF, unit, pos, parity, exhausted, queued, frank,
+                                   ftotal);
+      if (queued) fin_queue<SAMPLER>(fq, fq_n + frank, P, R);  // (before refill_one reuses P)
+      fq_n += ftotal;
+      if (push) store_entry<SAMPLER, FWD>(wp.out, pos, P, R);
+      if (parked) copy_entry(wp.in, i, wp.out, pos);
+    }
 #ifdef IZPI_SHADE_CLOCKS
     t1 = __builtin_readcyclecounter();
     k_push += t1 - t0;
@@ -648,6 +762,13 @@ k_shade(const DevScene sc, const ShadeParams sp, const WaveParams wp) {
   if (DEFER && fq_n) {
     __syncthreads();
     fin_flush<SAMPLER, MATSET>(sp, fq, fq_n);
+  }
+  if constexpr (STAGE) {
+    if (st_phase) {  // an odd trip count: the last iteration's entries are still staged
+      uint32_t rbase, rank;
+      block_reserve_fwd(wp.out_count, false, st_n, rbase, rank);
+      stage_flush(wp.out, rbase, st_n);
+    }
   }
   const uint32_t lane = threadIdx.x & 63;
 #ifdef IZPI_SHADE_CLOCKS
@@ -887,6 +1008,24 @@ int run_chunks(izpi_ctx* ctx, const izpi_render_req* req, const DevScene& sc, co
   const size_t dyn = sc.lds_bytes;  // the staged tables' LDS arena (render_body)
   int rc = resident_blocks(ctx, k_shade<SAMPLER, MATSET, FWD>, &shade_res, (int)SHADE_THREADS, dyn);
   if (rc) return rc;
+  // The staged form (k_shade<..., STAGE>): a forward Colour render without overflow blocks
+  // whose arena holds the Colour tables alone (no Spectral tables, no primitives in LDS: the
+  // stage lies behind them), whose entries are the arrays stage_flush writes, and whose
+  // blocks stay as many per CU with the stage's LDS as without.
+  bool stage = false;
+  const char* form = "plain (no staged instance)";
+  if constexpr (shade_can_stage(SAMPLER, MATSET, FWD)) {
+    if (tu.flags & IZPI_TUNE_NO_SHADE_STAGE) form = "plain (IZPI_TUNE_NO_SHADE_STAGE)";
+    else if (sp.rec_pool || sc.lds_bytes != lds_off::COLOUR_END) form = "plain (LDS arena)";
+    else if (wp.out.time || wp.out.blk || wp.out.cold || !wp.out.thr) form = "plain (entry arrays)";
+    else {
+      int stage_res = 0;
+      if ((rc = resident_blocks(ctx, k_shade<SAMPLER, MATSET, FWD, true>, &stage_res, (int)SHADE_THREADS, dyn + lds_off::STG_BYTES))) return rc;
+      stage = stage_res == shade_res;
+      form = stage ? "staged" : "plain (occupancy)";
+    }
+  }
+  if (tu.flags & IZPI_TUNE_PASS_LOG) fprintf(stderr, "IZPI_SHADE_FORM %s\n", form);
   // tail kernel: used once every unit has started and at most `tail_max` paths remain
   const bool tail_deep = ctx->stack_needed > 32;
   int tail_res = 0;
@@ -955,7 +1094,13 @@ int run_chunks(izpi_ctx* ctx, const izpi_render_req* req, const DevScene& sc, co
         launch_trace(ctx, sc, tr, wp, st, ctx->d_spill);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(ctx->evb[3 * b + 1], st));
-        hipLaunchKernelGGL((k_shade<SAMPLER, MATSET, FWD>), dim3(shade_res), dim3(SHADE_THREADS), dyn, st, sc, sp, wp);
+        bool launched = false;
+        if constexpr (shade_can_stage(SAMPLER, MATSET, FWD))
+          if (stage) {
+            hipLaunchKernelGGL((k_shade<SAMPLER, MATSET, FWD, true>), dim3(shade_res), dim3(SHADE_THREADS), dyn + lds_off::STG_BYTES, st, sc, sp, wp);
+            launched = true;
+          }
+        if (!launched) hipLaunchKernelGGL((k_shade<SAMPLER, MATSET, FWD>), dim3(shade_res), dim3(SHADE_THREADS), dyn, st, sc, sp, wp);
         HIP_TRY(hipGetLastError());
         if constexpr (FWD) {
           hipLaunchKernelGGL(k_refill_plan, dim3(1), dim3(1), 0, st, sp, wp.out_count, misc(ctx, 5));
@@ -1042,7 +1187,15 @@ int prepare_sampler(izpi_ctx* ctx, bool compact) {
     if ((rc = resident_blocks(ctx, tail32, &blocks))) return;
     rc = resident_blocks(ctx, tail64, &blocks);
   };
-#define IZPI_Q(M) query(k_shade<SAMPLER, M, FWD>, k_tail<SAMPLER, M, 32, FWD>, k_tail<SAMPLER, M, 64, FWD>)
+  auto query_staged = [&](auto shade) {  // the staged form of the forward Colour instances
+    if (!rc) rc = resident_blocks(ctx, shade, &blocks, (int)SHADE_THREADS);
+  };
+  (void)query_staged;
+#define IZPI_Q(M)                                                                                             \
+  do {                                                                                                        \
+    query(k_shade<SAMPLER, M, FWD>, k_tail<SAMPLER, M, 32, FWD>, k_tail<SAMPLER, M, 64, FWD>);                \
+    if constexpr (shade_can_stage(SAMPLER, M, FWD)) query_staged(k_shade<SAMPLER, M, FWD, true>);             \
+  } while (0)
   bool done = false;
   if constexpr (SAMPLER == IZPI_SAMPLER_COLOUR && !FWD)
     if (compact) { IZPI_Q(MATSET_CONST); done = true; }
