@@ -134,6 +134,43 @@ int izpi_host_assemble_shares(uint32_t width, uint32_t height, const uint32_t* t
  * codes as izpi_gpu_gomath); used by the parity tests. */
 double izpi_host_gomath(int op, double x, double y);
 
+/* ======================================================================
+ * The DISPLACE geometry operator: displacement.ApplyDisplacementMap
+ * (displacement/displacement.go:143-280) over `n` triangles and a float64 NRGBA map
+ * (row 0 = top; its blue channel is the height, read as ImageTxt.Value reads it,
+ * texture/image.go:73-101). Every triangle is tessellated at least once, adaptively and
+ * level by level, and each finished triangle is displaced along its own normal by
+ * dmin + (dmax - dmin) * z. The result is izpi_tri_in again: the displaced vertices, the
+ * child's UVs and the source's material.
+ *
+ * order: IZPI_DISPLACE_PER_TRIANGLE = one ApplyDisplacementMap per source triangle, as the
+ * scene path calls it (transport.go:641): outputs are source-major; IZPI_DISPLACE_MESH =
+ * one call over the whole mesh (wavefront.go:347): outputs are level-major across the
+ * mesh. In both, a level's outputs follow the parents' order times child 0..3.
+ *
+ * One deviation: where the reference would subdivide without end (a map that steps by more
+ * than 2/|dmax-dmin| between two neighbouring texels), a source triangle that still has
+ * work after IZPI_DISPLACE_MAX_LEVELS levels fails the whole call with
+ * IZPI_ERR_UNSUPPORTED.
+ *
+ * out == NULL counts only. *n_out receives the number of output triangles; when out holds
+ * fewer (cap), the call returns IZPI_ERR_INVALID with *n_out set. counts (may be NULL)
+ * receives the outputs per source triangle, [n]. *ms (may be NULL): the device time
+ * between upload and copy back (izpi_gpu_displace), the wall time (izpi_host_displace).
+ * The device entry keeps its buffers for the call only and refuses, without trying, a
+ * request whose work lists could exceed half of the free device memory. The host entry is
+ * the sequential twin, bit for bit; its error is izpi_host_last_error's.
+ * ====================================================================== */
+#define IZPI_DISPLACE_PER_TRIANGLE 0u
+#define IZPI_DISPLACE_MESH 1u
+#define IZPI_DISPLACE_MAX_LEVELS 16
+int izpi_gpu_displace(izpi_ctx* ctx, const izpi_tri_in* tris, uint64_t n, const double* rgba, uint32_t width,
+                      uint32_t height, double dmin, double dmax, uint32_t order, izpi_tri_in* out, uint64_t cap,
+                      uint64_t* n_out, uint64_t* counts, double* ms);
+int izpi_host_displace(const izpi_tri_in* tris, uint64_t n, const double* rgba, uint32_t width, uint32_t height,
+                       double dmin, double dmax, uint32_t order, izpi_tri_in* out, uint64_t cap, uint64_t* n_out,
+                       uint64_t* counts, double* ms);
+
 /* sizeof() of the boundary structs: 0 izpi_bvh4_node 1 izpi_texture 2 izpi_material
  * 3 izpi_camera 4 izpi_scene_desc 5 izpi_render_req 6 izpi_render_stats 7 izpi_hit
  * 8 izpi_tri_in 9 izpi_sphere_in 10 izpi_camera_in 11 izpi_scene_input 12 izpi_proto_info
@@ -179,6 +216,16 @@ int izpi_scene_info(const izpi_proto_scene* s, izpi_proto_info* out);
 const char* izpi_scene_image_file(const izpi_proto_scene* s, uint32_t i);
 /* ...and hands over as float64 NRGBA texels, row 0 = top (texture.ImageTxt). */
 int izpi_scene_set_image(izpi_proto_scene* s, const char* filename, uint32_t width, uint32_t height, const double* rgba);
+/* Filenames of Scene.displacement_maps, which the host decodes (leader.go:100-109)... */
+const char* izpi_scene_displacement_file(const izpi_proto_scene* s, uint32_t i);
+/* ...and hands over as float64 NRGBA texels, row 0 = top; maps are keyed by filename.
+ * Width and height are at least 1. */
+int izpi_scene_set_displacement_map(izpi_proto_scene* s, const char* filename, uint32_t width, uint32_t height,
+                                    const double* rgba);
+/* Where izpi_scene_to_input runs triangles with `operator: DISPLACE`: on ctx's device
+ * (izpi_gpu_displace), or with NULL, the default, on the host (izpi_host_displace). Both
+ * give the same triangles. The context must outlive the conversions that use it. */
+int izpi_scene_set_displacer(izpi_proto_scene* s, izpi_ctx* ctx);
 /* Streamed triangles (transport.go:574-583, e.g. from izpi_obj_group_to_triangles);
  * `material` of each izpi_tri_in is ignored, the name is resolved at conversion. */
 int izpi_scene_add_triangles(izpi_proto_scene* s, const izpi_tri_in* tris, uint64_t n, const char* material_name);
@@ -186,8 +233,11 @@ int izpi_scene_add_triangles(izpi_proto_scene* s, const izpi_tri_in* tris, uint6
 uint32_t izpi_scene_background(const izpi_proto_scene* s, double* wavelengths, double* values, uint32_t max);
 /* transport.ToScene (transport.go:53-92) up to the BVH build: materials (registered by
  * Material.name), textures, light-source library, camera, embedded then streamed
- * triangles, spheres. *out stays valid until the next call or izpi_scene_free; pass
- * it to izpi_host_build_scene. */
+ * triangles, spheres. An embedded triangle with `operator: DISPLACE` is replaced, in its
+ * place, by what displacement.ApplyDisplacementMap returns for it (transport.go:634-646);
+ * its map must be declared in Scene.displacement_maps and handed over, else
+ * IZPI_ERR_INVALID "displacement map <name> not found". *out stays valid until the next
+ * call or izpi_scene_free; pass it to izpi_host_build_scene. */
 int izpi_scene_to_input(izpi_proto_scene* s, double aspect_override, uint64_t bvh_seed, const izpi_scene_input** out);
 /* name of material i of the last izpi_scene_to_input */
 const char* izpi_scene_material_name(const izpi_proto_scene* s, uint32_t i);

@@ -33,6 +33,8 @@ HOST_SKIP_BVH = 1
 BVH_LBVH, BVH_PLOC = 0, 1
 BVH_SAH = 0x100  # flag: collapse by the surface-area cost model (PLOC only)
 BVH_PLOC_SAH = BVH_PLOC | BVH_SAH
+DISPLACE_PER_TRIANGLE, DISPLACE_MESH = 0, 1
+DISPLACE_MAX_LEVELS = 16
 
 
 def prim_ref(kind, idx):
@@ -215,6 +217,8 @@ EXPORTS = [
     "izpi_obj_parse", "izpi_obj_info_get", "izpi_obj_copy_vertices", "izpi_obj_group_get", "izpi_obj_copy_faces",
     "izpi_obj_material_get", "izpi_obj_translate", "izpi_obj_scale", "izpi_obj_rotate",
     "izpi_obj_group_to_triangles", "izpi_obj_free",
+    "izpi_gpu_displace", "izpi_host_displace", "izpi_scene_displacement_file", "izpi_scene_set_displacement_map",
+    "izpi_scene_set_displacer",
 ]
 
 _lib = None
@@ -307,6 +311,15 @@ def lib():
     L.izpi_scene_image_file.argtypes = [vp, C.c_uint32]
     L.izpi_scene_image_file.restype = C.c_char_p
     L.izpi_scene_set_image.argtypes = [vp, C.c_char_p, C.c_uint32, C.c_uint32, c_double_p]
+    L.izpi_scene_displacement_file.argtypes = [vp, C.c_uint32]
+    L.izpi_scene_displacement_file.restype = C.c_char_p
+    L.izpi_scene_set_displacement_map.argtypes = [vp, C.c_char_p, C.c_uint32, C.c_uint32, c_double_p]
+    L.izpi_scene_set_displacer.argtypes = [vp, vp]
+    c_uint64_p = C.POINTER(C.c_uint64)
+    displace_args = [vp, C.c_uint64, c_double_p, C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_uint32, vp,
+                     C.c_uint64, c_uint64_p, c_uint64_p, c_double_p]
+    L.izpi_host_displace.argtypes = displace_args
+    L.izpi_gpu_displace.argtypes = [vp] + displace_args
     L.izpi_scene_add_triangles.argtypes = [vp, vp, C.c_uint64, C.c_char_p]
     L.izpi_scene_background.argtypes = [vp, c_double_p, c_double_p, C.c_uint32]
     L.izpi_scene_background.restype = C.c_uint32

@@ -1582,6 +1582,30 @@ int izpi_gpu_build_bvh4(izpi_ctx* ctx, const double* boxes, uint32_t n, uint32_t
   return IZPI_OK;
 }
 
+}  // extern "C"
+namespace izpi_displace {  // displace.hip
+int run(hipStream_t st, const izpi_tri_in* tris, uint64_t n, const double* rgba, uint32_t width, uint32_t height,
+        double dmin, double dmax, uint32_t order, izpi_tri_in* out, uint64_t cap, uint64_t* n_out, uint64_t* counts,
+        double* ms, std::string& err);
+const char* check(const izpi_tri_in* tris, uint64_t n, const double* rgba, uint32_t width, uint32_t height,
+                  uint32_t order, const uint64_t* n_out);
+}
+extern "C" {
+
+int izpi_gpu_displace(izpi_ctx* ctx, const izpi_tri_in* tris, uint64_t n, const double* rgba, uint32_t width,
+                      uint32_t height, double dmin, double dmax, uint32_t order, izpi_tri_in* out, uint64_t cap,
+                      uint64_t* n_out, uint64_t* counts, double* ms) {
+  if (!ctx) return IZPI_ERR_INVALID;
+  if (n_out) *n_out = 0;
+  if (const char* bad = izpi_displace::check(tris, n, rgba, width, height, order, n_out)) {
+    ctx->err = bad;
+    return IZPI_ERR_INVALID;
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  return izpi_displace::run(ctx->stream, tris, n, rgba, width, height, dmin, dmax, order, out, cap, n_out, counts, ms,
+                            ctx->err);
+}
+
 int izpi_gpu_postprocess(izpi_ctx* ctx, double* canvas_dev, uint32_t width, uint32_t height, const uint32_t* filters,
                          const double* params, uint32_t num_filters) {
   if (!ctx) return IZPI_ERR_INVALID;

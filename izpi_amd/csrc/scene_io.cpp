@@ -722,6 +722,10 @@ struct izpi_proto_scene {
   std::map<std::string, std::vector<double>> images;            // filename -> W*H*4 float64 NRGBA
   std::vector<std::pair<std::string, std::vector<izpi_tri_in>>> streamed;  // transport.go:574-583
   std::vector<std::string> image_files;                          // image_textures values' filenames
+  std::vector<std::string> displacement_files;                   // displacement_maps values' filenames
+  struct DMap { uint32_t w = 0, h = 0; std::vector<double> rgba; };
+  std::map<std::string, DMap> dmaps;                             // filename -> float64 NRGBA (leader.go:100-109)
+  izpi_ctx* displacer = nullptr;                                 // DISPLACE runs there; null: on the host
   std::string name, version, warnings;
   // built by izpi_scene_to_input
   std::vector<izpi_tri_in> tris;
@@ -998,14 +1002,80 @@ struct Converter {
     };
     const PMsg* objs = sc.msg("objects");
     if (objs) {
+      // toSceneTriangle (transport.go:600-649). A DISPLACE triangle becomes the triangles
+      // displacement.ApplyDisplacementMap returns for it alone (transport.go:641). They are
+      // computed once per (map, min, max) group, in per-triangle order, and each source's run
+      // then takes the source's place in transport order.
+      struct Group {
+        const izpi_proto_scene::DMap* map;
+        double dmin, dmax;
+        std::vector<izpi_tri_in> src, out;
+        std::vector<uint64_t> counts, start;
+      };
+      std::vector<Group> groups;
+      std::vector<izpi_tri_in> plain;
+      struct Slot { int group; size_t index; };  // group < 0: plain[index]
+      std::vector<Slot> slots;
       for (auto& t : objs->all("triangles")) {
         const PMsg* tm = t.m.get();
         const uint32_t mat = lookup(tm->str("material_name"));
-        if (tm->u("operator") == 1)
-          fail(IZPI_ERR_UNSUPPORTED, "triangle DISPLACE operator (displacement maps are outside the GPU path)");
         izpi_tri_in o;
         tri(tm, mat, o);
-        s.tris.push_back(o);
+        if (tm->u("operator") != 1) {
+          slots.push_back(Slot{-1, plain.size()});
+          plain.push_back(o);
+          continue;
+        }
+        const PMsg* dm = tm->msg("displace");
+        const std::string name = dm ? dm->str("displacement_map") : std::string();
+        const double dmin = dm ? dm->num("min") : 0.0, dmax = dm ? dm->num("max") : 0.0;
+        const bool declared =
+            std::find(s.displacement_files.begin(), s.displacement_files.end(), name) != s.displacement_files.end();
+        auto it = s.dmaps.find(name);
+        if (!declared || it == s.dmaps.end()) invalid("triangle DISPLACE operator: displacement map " + name + " not found");
+        int g = -1;
+        for (size_t k = 0; k < groups.size(); k++)
+          if (groups[k].map == &it->second && !memcmp(&groups[k].dmin, &dmin, 8) && !memcmp(&groups[k].dmax, &dmax, 8))
+            g = (int)k;
+        if (g < 0) {
+          groups.push_back(Group{&it->second, dmin, dmax, {}, {}, {}, {}});
+          g = (int)groups.size() - 1;
+        }
+        slots.push_back(Slot{g, groups[g].src.size()});
+        groups[g].src.push_back(o);
+      }
+      uint64_t total = plain.size();
+      for (Group& g : groups) {
+        const uint64_t n = g.src.size();
+        g.counts.assign(n, 0);
+        uint64_t n_out = 0;
+        auto call = [&](izpi_tri_in* out, uint64_t cap) {
+          const int rc = s.displacer
+                             ? izpi_gpu_displace(s.displacer, g.src.data(), n, g.map->rgba.data(), g.map->w, g.map->h, g.dmin,
+                                                 g.dmax, IZPI_DISPLACE_PER_TRIANGLE, out, cap, &n_out, g.counts.data(), nullptr)
+                             : izpi_host_displace(g.src.data(), n, g.map->rgba.data(), g.map->w, g.map->h, g.dmin, g.dmax,
+                                                  IZPI_DISPLACE_PER_TRIANGLE, out, cap, &n_out, g.counts.data(), nullptr);
+          if (rc)
+            fail(rc, std::string("triangle DISPLACE operator: ") +
+                         (s.displacer ? izpi_gpu_last_error(s.displacer) : izpi_host_last_error()));
+        };
+        call(nullptr, 0);  // count first: the result must fit num_tris before it is produced
+        total += n_out;
+        if (total > 0xFFFFFFFFull) invalid("triangle DISPLACE operator: more than 2^32 - 1 triangles");
+        g.out.resize(n_out);
+        call(g.out.data(), n_out);
+        g.start.assign(n + 1, 0);
+        for (uint64_t k = 0; k < n; k++) g.start[k + 1] = g.start[k] + g.counts[k];
+        if (g.start[n] != n_out) invalid("triangle DISPLACE operator: the per-source counts do not add up");
+      }
+      s.tris.reserve(total);
+      for (const Slot& sl : slots) {
+        if (sl.group < 0) {
+          s.tris.push_back(plain[sl.index]);
+        } else {
+          const Group& g = groups[sl.group];
+          s.tris.insert(s.tris.end(), g.out.begin() + g.start[sl.index], g.out.begin() + g.start[sl.index + 1]);
+        }
       }
     }
     for (auto& group : s.streamed) {
@@ -1041,6 +1111,7 @@ struct Converter {
     in.camera.time0 = getf(cam, "time0");
     in.camera.time1 = getf(cam, "time1");
     in.camera.exposure = getf(cam, "exposure");
+    if (s.tris.size() > 0xFFFFFFFFull) invalid("more than 2^32 - 1 triangles");
     in.num_tris = (uint32_t)s.tris.size();
     in.num_spheres = (uint32_t)s.spheres.size();
     in.num_materials = (uint32_t)s.mats.size();
@@ -1067,6 +1138,10 @@ int finish_parse(std::shared_ptr<PMsg> root, izpi_proto_scene** out) {
   for (auto& e : s->root->all("image_textures")) {
     const PMsg* v = e.m->msg("value");
     s->image_files.push_back(v ? v->str("filename") : std::string());
+  }
+  for (auto& e : s->root->all("displacement_maps")) {
+    const PMsg* v = e.m->msg("value");
+    s->displacement_files.push_back(v ? v->str("filename") : std::string());
   }
   memset(&s->input, 0, sizeof s->input);
   *out = s;
@@ -1309,6 +1384,32 @@ int izpi_scene_set_image(izpi_proto_scene* s, const char* filename, uint32_t wid
     if (!s || !filename || (!rgba && width && height)) invalid("null argument");
     s->images[filename].assign(rgba, rgba + (size_t)width * height * 4);
     s->image_dims[filename] = {width, height};
+    return IZPI_OK;
+  });
+}
+
+const char* izpi_scene_displacement_file(const izpi_proto_scene* s, uint32_t i) {
+  return (s && i < s->displacement_files.size()) ? s->displacement_files[i].c_str() : nullptr;
+}
+
+int izpi_scene_set_displacement_map(izpi_proto_scene* s, const char* filename, uint32_t width, uint32_t height,
+                                    const double* rgba) {
+  return guarded([&] {
+    if (!s || !filename) invalid("null argument");
+    if (width < 1 || height < 1) invalid("a displacement map needs width and height of at least 1");
+    if (!rgba) invalid("null argument");
+    izpi_proto_scene::DMap& m = s->dmaps[filename];
+    m.w = width;
+    m.h = height;
+    m.rgba.assign(rgba, rgba + (size_t)width * height * 4);
+    return IZPI_OK;
+  });
+}
+
+int izpi_scene_set_displacer(izpi_proto_scene* s, izpi_ctx* ctx) {
+  return guarded([&] {
+    if (!s) invalid("null argument");
+    s->displacer = ctx;
     return IZPI_OK;
   });
 }

@@ -111,10 +111,38 @@ class ProtoScene:
             L.izpi_scene_background(self.handle, wl.ctypes.data_as(N.c_double_p), val.ctypes.data_as(N.c_double_p), n)
         return wl, val
 
-    def to_input(self, aspect_override=0.0, bvh_seed=12345):
+    def displacement_files(self):
+        """Filenames of Scene.displacement_maps, which the caller decodes (leader.go:100-109)."""
+        L = N.lib()
+        return [L.izpi_scene_displacement_file(self.handle, i).decode()
+                for i in range(self.info()["num_displacement_maps"])]
+
+    def set_displacement_map(self, filename, rgba):
+        """Hand over a decoded displacement map: (H, W, 4) float64 NRGBA, row 0 = top."""
+        a = np.ascontiguousarray(rgba, np.float64)
+        assert a.ndim == 3 and a.shape[2] == 4
+        _err(N.lib().izpi_scene_set_displacement_map(self.handle, filename.encode(), a.shape[1], a.shape[0],
+                                                     a.ctypes.data_as(N.c_double_p)), "izpi_scene_set_displacement_map")
+
+    def set_displacer(self, ctx):
+        """Run DISPLACE triangles on the device of `ctx` (an izpi_ctx handle, e.g.
+        GPURenderer.ctx) in every later to_input(); None: on the host (the default)."""
+        _err(N.lib().izpi_scene_set_displacer(self.handle, ctx), "izpi_scene_set_displacer")
+        self._displacer = ctx
+
+    def to_input(self, aspect_override=0.0, bvh_seed=12345, displacer=None):
+        """transport.ToScene up to the BVH build. displacer: an izpi_ctx handle for this
+        conversion's DISPLACE triangles (None: what set_displacer chose, by default the host)."""
+        before = getattr(self, "_displacer", None)
+        if displacer is not None:
+            self.set_displacer(displacer)
         p = C.POINTER(N.SceneInput)()
-        _err(N.lib().izpi_scene_to_input(self.handle, float(aspect_override), int(bvh_seed), C.byref(p)),
-             "izpi_scene_to_input")
+        try:
+            _err(N.lib().izpi_scene_to_input(self.handle, float(aspect_override), int(bvh_seed), C.byref(p)),
+                 "izpi_scene_to_input")
+        finally:
+            if displacer is not None:
+                self.set_displacer(before)
         return _ProtoInput(p, self)
 
     def material_names(self):
@@ -136,6 +164,43 @@ class ProtoScene:
             self.close()
         except Exception:
             pass
+
+
+def displace(tris, rgba, dmin, dmax, order=N.DISPLACE_PER_TRIANGLE, ctx=None, count_only=False, timing=None):
+    """displacement.ApplyDisplacementMap over `tris` (TRI_DTYPE) and a (H, W, 4) float64 NRGBA
+    map: adaptive tessellation, then displacement along each finished triangle's normal by
+    dmin + (dmax - dmin) * blue. order: N.DISPLACE_PER_TRIANGLE (one call per source triangle,
+    the scene path's order) or N.DISPLACE_MESH (one call over the mesh, level-major).
+
+    With `ctx` (an izpi_ctx handle, e.g. GPURenderer.ctx) it runs on that device
+    (izpi_gpu_displace), without one on the host (izpi_host_displace): same triangles, bit
+    for bit. Returns (triangles, per-source counts); count_only leaves the triangles empty.
+    timing: a dict that receives "ms" (device time on the GPU, wall time on the host)."""
+    L = N.lib()
+    t = np.ascontiguousarray(tris, TRI_DTYPE)
+    a = np.ascontiguousarray(rgba, np.float64)
+    assert a.ndim == 3 and a.shape[2] == 4
+    counts = np.zeros(max(1, len(t)), np.uint64)
+    n_out, ms = C.c_uint64(), C.c_double()
+
+    def call(out, cap):
+        args = (t.ctypes.data if t.size else None, len(t), a.ctypes.data_as(N.c_double_p), a.shape[1], a.shape[0],
+                float(dmin), float(dmax), int(order), out, cap, C.byref(n_out), counts.ctypes.data_as(C.POINTER(C.c_uint64)),
+                C.byref(ms))
+        if ctx is None:
+            _err(L.izpi_host_displace(*args), "izpi_host_displace")
+        else:
+            rc = L.izpi_gpu_displace(ctx, *args)
+            if rc != 0:
+                raise RuntimeError("izpi_gpu_displace failed (status %d): %s" % (rc, L.izpi_gpu_last_error(ctx).decode()))
+
+    call(None, 0)
+    out = np.zeros(0 if count_only else n_out.value, TRI_DTYPE)
+    if out.size:
+        call(out.ctypes.data, len(out))
+    if timing is not None:
+        timing["ms"] = ms.value
+    return out, counts[:len(t)].copy()
 
 
 def light_source(name):
