@@ -320,8 +320,12 @@ IZPI_DEV bool slab(float mnx, float mny, float mnz, float mxx, float mxy, float 
 // The subtract and multiply run as packed f32 pairs (children 0-1 and 2-3), min3/max3
 // fold the three axes.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-IZPI_DEV uint32_t slab4_fast(float4 mnx, float4 mny, float4 mnz, float4 mxx, float4 mxy, float4 mxz, float ox, float oy,
-                             float oz, float ix, float iy, float iz, float tmax) {
+// The result is four wave masks (bit l of h[i]: lane l hits slot i; inactive lanes 0), not a
+// bit field per lane: each compare already leaves a lane mask, its ballot is that mask, and the
+// caller combines masks on the scalar unit. (The ballot of a conjunction is built the long way,
+// through a 0 / 1 register and a second compare: hence one ballot per compare.)
+IZPI_DEV void slab4_fast(float4 mnx, float4 mny, float4 mnz, float4 mxx, float4 mxy, float4 mxz, float ox, float oy,
+                         float oz, float ix, float iy, float iz, float tmax, uint64_t (&h)[4]) {
   const f32x2 o_x = {ox, ox}, o_y = {oy, oy}, o_z = {oz, oz};
   const f32x2 i_x = {ix, ix}, i_y = {iy, iy}, i_z = {iz, iz};
   const f32x2 a0x = (f32x2{mnx.x, mnx.y} - o_x) * i_x, a1x = (f32x2{mnx.z, mnx.w} - o_x) * i_x;
@@ -333,16 +337,14 @@ IZPI_DEV uint32_t slab4_fast(float4 mnx, float4 mny, float4 mnz, float4 mxx, flo
   const float t0x[4] = {a0x.x, a0x.y, a1x.x, a1x.y}, t1x[4] = {b0x.x, b0x.y, b1x.x, b1x.y};
   const float t0y[4] = {a0y.x, a0y.y, a1y.x, a1y.y}, t1y[4] = {b0y.x, b0y.y, b1y.x, b1y.y};
   const float t0z[4] = {a0z.x, a0z.y, a1z.x, a1z.y}, t1z[4] = {b0z.x, b0z.y, b1z.x, b1z.y};
-  uint32_t m = 0;
 #pragma unroll
   for (int i = 0; i < 4; i++) {
     const float tn = __builtin_fmaxf(__builtin_fmaxf(__builtin_fminf(t0x[i], t1x[i]), __builtin_fminf(t0y[i], t1y[i])),
                                      __builtin_fminf(t0z[i], t1z[i]));
     const float tf = __builtin_fminf(__builtin_fminf(__builtin_fmaxf(t0x[i], t1x[i]), __builtin_fmaxf(t0y[i], t1y[i])),
                                      __builtin_fmaxf(t0z[i], t1z[i]));
-    m |= (tn <= tf && tf >= 0.0f && tn <= tmax) ? (1u << i) : 0u;
+    h[i] = __builtin_amdgcn_ballot_w64(tn <= tf) & __builtin_amdgcn_ballot_w64(tf >= 0.0f) & __builtin_amdgcn_ballot_w64(tn <= tmax);
   }
-  return m;
 }
 IZPI_DEV bool ray_fast_ok(float ox, float oy, float oz, float ix, float iy, float iz) {
   const float inf = __builtin_huge_valf();
@@ -373,22 +375,25 @@ IZPI_DEV bool tri_intersect(const double* a, V3 o, V3 d, double tmin, double tma
 // The same test without the final `t > tMax` rejection: that last comparison is the
 // only one that depends on tMax, so tests of one leaf can run in parallel and be
 // accepted afterwards in primitive order against the running tMax (bit-identical).
+// It has no early returns: every product is computed and the four rejections are combined at
+// the end. A lane that passes runs tri_intersect's operations on the same operands, and a lane
+// that fails returns false whatever its later values are (a zero determinant only makes them
+// infinite or NaN). In a wave of up to 64 tests some lane passes each rejection nearly always,
+// so an early return skips nothing; but each one is a divergent branch, and the compiler sinks
+// the loads of v0 behind the first, a second dependent round trip to memory in every step.
 IZPI_DEV bool tri_intersect_no_tmax(const double* a, V3 o, V3 d, double tmin, double& t, double& u, double& v) {
   const double eps = 1e-8;
   V3 v0 = mk(a[0], a[1], a[2]), e1 = mk(a[3], a[4], a[5]), e2 = mk(a[6], a[7], a[8]);
   V3 h = cross(d, e2);
   double aa = dot(e1, h);
-  if (gm::abs(aa) < eps) return false;
   double f = 1.0 / aa;
   V3 s = sub(o, v0);
   u = f * dot(s, h);
-  if (u < -eps || u > 1.0 + eps) return false;
   V3 q = cross(s, e1);
   v = f * dot(d, q);
-  if (v < -eps || u + v > 1.0 + eps) return false;
   t = f * dot(e2, q);
-  if (t < tmin) return false;
-  return true;
+  const bool r0 = gm::abs(aa) < eps, r1 = (u < -eps) | (u > 1.0 + eps), r2 = (v < -eps) | (u + v > 1.0 + eps), r3 = t < tmin;
+  return !(r0 | r1 | r2 | r3);
 }
 // Sphere.center (sphere.go:495-497)
 IZPI_DEV V3 sph_center(const double* a, double time) {

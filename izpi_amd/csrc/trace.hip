@@ -28,6 +28,13 @@
 // decoded into the same f32 boxes the 128-B records of a quantised scene hold; the slab test
 // and everything after it are unchanged.
 constexpr uint32_t BVH_LDS_BYTES = 4096;
+// This lane's bit of a wave mask, as a condition (the mask becomes the select's lane mask).
+__device__ __forceinline__ bool lane_of(uint64_t mask) { return __builtin_amdgcn_inverse_ballot_w64(mask); }
+// Set bits of a wave mask below this lane: v_mbcnt_lo / v_mbcnt_hi, two instructions where
+// __popcll(mask & ((1ull << lane) - 1)) compiles to two ANDs and two popcounts.
+__device__ __forceinline__ uint32_t lanes_below(uint64_t mask) {
+  return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
 template <int S, int WPE, bool DIST, bool TRI, bool LB, bool RL, bool Q>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) k_trace2(const DevScene sc, const WaveParams wp, unsigned long long* counters,
                                                 uint32_t* err, int32_t* spill, uint32_t spill_stride, uint32_t prim_w,
@@ -101,10 +108,17 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
   double tmax = 0;
   float ix = 0, iy = 0, iz = 0, ox = 0, oy = 0, oz = 0;
   int32_t cur = -1, pk = 0, pend = 0;
-  int sp = 0, low = 0;
+  // The wave's mode masks are ballots of single compares on these registers (a compare leaves
+  // its lane mask as it is; the ballot of a boolean that went through a join is rebuilt through
+  // a 0 / 1 register and a second compare): sp < 0 marks an idle lane (busy == (sp >= 0)), and
+  // a lane scans a leaf exactly while pk < pend ((busy && in_prim) == (pk < pend): a leaf holds
+  // at least one primitive, and pk == pend once it is done).
+  int sp = -1, low = 0;
   int clean_from = 0;     // stack entries at positions >= clean_from were pushed after the last accepted hit
   int32_t bprim = -1;
   bool fast = false;      // slab4_fast is exact for this ray
+  uint64_t m_slow = ~0ull;  // wave mask of !fast, renewed by each refill (wave-uniform)
+  bool any_spill = false; // a lane of this wave has spilled ring entries (wave-uniform)
 #ifdef IZPI_SHADOW
   // measurement: spilled stack entries stored / loaded (wave counts), and a sink for the
   // shadow loads (bit 1: inner nodes, 2: leaf records, 4: primitives)
@@ -120,9 +134,18 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
 #else
 #define IZPI_CLK(v) (void)0
 #endif
+  // measurement builds only (tools/step_counts.py): section markers in the assembly; they emit
+  // no instruction
+#ifdef IZPI_STEP_MARKS
+#define IZPI_MARK(name) asm volatile("; IZPI_MARK " name)
+#else
+#define IZPI_MARK(name) (void)0
+#endif
   for (;;) {
     IZPI_CLK(k0);
-    const uint64_t idle = __ballot(!busy);
+    IZPI_MARK("head");
+    const uint64_t idle = __builtin_amdgcn_ballot_w64(sp < 0);
+    uint64_t idle_now = idle;  // the idle lanes after this iteration's refill
     if (idle != 0) {
       const uint32_t nidle = (uint32_t)__popcll(idle);
       if (!exhausted && (nidle >= refill_min || idle == ~0ull) && c_pos >= c_end) {
@@ -130,6 +153,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
         // entries with one atomic (a single head word saturates near 88 dequeues/us).
         // Every wave's first chunk is its own (chunk w, set before the loop), without an
         // atomic: a pass of at most nwaves chunks (the tail passes) dequeues without any.
+        IZPI_MARK("dequeue");
         uint32_t b = 0;
         if (lane == 0) b = atomicAdd(wp.trace_next, chunk);
         b = __builtin_amdgcn_readfirstlane(b) + nwaves * first;
@@ -138,11 +162,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
         c_end = b + chunk < n ? b + chunk : n;
       }
       if (!exhausted && (nidle >= refill_min || idle == ~0ull) && c_pos < c_end) {
+        IZPI_MARK("refill");
         const uint32_t take = nidle < c_end - c_pos ? nidle : c_end - c_pos;
         const uint32_t base = c_pos;
         c_pos += take;
         bool main_ray = false;
-        const uint32_t rank = (uint32_t)__popcll(idle & ((1ull << lane) - 1));
+        const uint32_t rank = lanes_below(idle);
         const uint32_t my = base + rank;
         if (!busy && rank < take) {
           const uint32_t k = read_kind ? sld(wp.in.kind + my) : (uint32_t)RAY_MAIN;
@@ -167,10 +192,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
             ox = (float)r.o[0]; oy = (float)r.o[1]; oz = (float)r.o[2];
             fast = sc.nan_free_bounds && ray_fast_ok(ox, oy, oz, ix, iy, iz);
             cur = sc.root;
-            sp = 0; low = 0; clean_from = 0;
+            busy = cur != -1;
+            sp = busy ? 0 : -1; low = 0; clean_from = 0;
             in_prim = false;
             bprim = -1;
-            busy = cur != -1;
             if (!busy) {
               if ((UVL || UVS) && wp.hit_uv) {  // (t, prim) and (u, v) interleaved: hs == 2
                 double2* rec = wp.in.hit + ((size_t)my << 1);
@@ -182,6 +207,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
           }
         }
         c_rays += (uint64_t)__popcll(__ballot(main_ray));
+        m_slow = __ballot(!fast);
+        idle_now = __builtin_amdgcn_ballot_w64(sp < 0);
         // drain the new rays' loads here: left pending they make the compiler wait for
         // vmcnt(0) at the loop head, i.e. for every hit-record store, on every iteration
         __builtin_amdgcn_s_waitcnt(0x0F70);
@@ -189,8 +216,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
         break;
       }
     }
-    const uint64_t m_prim = __ballot(busy && in_prim);
-    const uint64_t m_node = __ballot(busy && !in_prim);
+    IZPI_MARK("pick");
+    const uint64_t m_prim = __builtin_amdgcn_ballot_w64(pk < pend);
+    const uint64_t m_node = ~(m_prim | idle_now);
     if ((m_prim | m_node) == 0) continue;
     const uint32_t n_prim = (uint32_t)__popcll(m_prim), n_node = (uint32_t)__popcll(m_node);
     bool advance = false;   // lane finished its current node / leaf: take next or pop
@@ -202,17 +230,20 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
 #endif
     if (n_prim * prim_w >= n_node * 16u) {
       if constexpr (DIST) {
+        IZPI_MARK("prim");
         // ---- distributed primitive step: every pending test of the PRIM lanes' leaves
         // (up to 64) runs on its own lane, then each owner accepts its leaf's results in
         // primitive order against its running tMax (bvh4.go:123-134, triangle.go:219)
-        const uint32_t cnt = (busy && in_prim) ? (uint32_t)(pend - pk) : 0u;  // 1..4
-        const uint64_t lt = (1ull << lane) - 1;
-        const uint32_t base = (uint32_t)__popcll(__ballot(cnt & 1u) & lt) + 2u * (uint32_t)__popcll(__ballot(cnt & 2u) & lt) +
-                              4u * (uint32_t)__popcll(__ballot(cnt & 4u) & lt);
-        const bool served = cnt > 0 && base + cnt <= 64;
-        const uint64_t ms = __ballot(served);
+        const uint32_t cnt = (uint32_t)(pend - pk);  // 1..4, and 0 on the lanes that scan no leaf
+        // exclusive prefix sum of cnt over the wave: one ballot per bit of cnt, each counted
+        // below this lane by a v_mbcnt pair
+        const uint32_t base = lanes_below(__ballot(cnt & 1u)) + 2u * lanes_below(__ballot(cnt & 2u)) +
+                              4u * lanes_below(__ballot(cnt & 4u));
+        // (the first scanning lane is always served: the mask is not empty)
+        const uint64_t ms = m_prim & __builtin_amdgcn_ballot_w64(base + cnt <= 64);
+        const bool served = lane_of(ms);
         const int last = 63 - __clzll((long long)ms);
-        const uint32_t total = (uint32_t)__shfl((int)(base + cnt), last);
+        const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)(base + cnt), last);  // (wave-uniform)
         {  // a leaf has 1..4 primitives (bvh4.go:638): four predicated writes, no loop
           const uint32_t e = ((uint32_t)pk << 6) | lane;
           uint32_t* dq = dist_owner + wbase + base;
@@ -366,12 +397,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
       c_pstep++;
       }
     } else {
+      IZPI_MARK("node");
       c_nodes += n_node;
       c_nstep++;
       // ---- node step: visit `cur` (bvh4.go:87-146)
-      const bool wave_fast = __ballot(busy && !in_prim && !fast) == 0;
-      if (__ballot(busy && !in_prim && sp + 3 - low > S) != 0) {
+      const bool wave_fast = (m_node & m_slow) == 0;
+      if ((m_node & __builtin_amdgcn_ballot_w64(sp + 3 - low > S)) != 0) {
         // ring too full for this step's three writes: spill the oldest entries (rare)
+        any_spill = true;
         if (busy && !in_prim) {
           while (sp + 3 - low > S) {
             gsp[(size_t)low * spill_stride] = stk[(low & (S - 1)) * 256];
@@ -455,28 +488,34 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
         const float4 mxy = make_float4(is_leaf ? q1.x : mxy_.x, mxy_.y, mxy_.z, mxy_.w);
         const float4 mxz = make_float4(is_leaf ? q1.y : mxz_.x, mxz_.y, mxz_.z, mxz_.w);
         const int4 ch = make_int4(is_leaf ? cur : ch_.x, ch_.y, ch_.z, ch_.w);
-        uint32_t hm;
+        // The four slot results are wave masks (one bit per lane, as the compares leave them),
+        // combined on the scalar unit: a per-lane bit field costs the vector unit a select to
+        // build each bit and a compare to test it again at every use.
+        uint64_t hit[4];
         if (wave_fast) {
-          hm = slab4_fast(mnx, mny, mnz, mxx, mxy, mxz, ox, oy, oz, ix, iy, iz, tm);
+          slab4_fast(mnx, mny, mnz, mxx, mxy, mxz, ox, oy, oz, ix, iy, iz, tm, hit);
         } else {
           const float amnx[4] = {mnx.x, mnx.y, mnx.z, mnx.w}, amny[4] = {mny.x, mny.y, mny.z, mny.w},
                       amnz[4] = {mnz.x, mnz.y, mnz.z, mnz.w}, amxx[4] = {mxx.x, mxx.y, mxx.z, mxx.w},
                       amxy[4] = {mxy.x, mxy.y, mxy.z, mxy.w}, amxz[4] = {mxz.x, mxz.y, mxz.z, mxz.w};
-          hm = 0;
 #pragma unroll
           for (int i = 0; i < 4; i++)
-            if (slab(amnx[i], amny[i], amnz[i], amxx[i], amxy[i], amxz[i], ox, oy, oz, ix, iy, iz, tm)) hm |= 1u << i;
+            hit[i] = __builtin_amdgcn_ballot_w64(slab(amnx[i], amny[i], amnz[i], amxx[i], amxy[i], amxz[i], ox, oy, oz, ix, iy, iz, tm));
         }
         // slots 0..3 with ChildIndex != -1 whose box is hit (bvh4.go:119-146): the first
         // is visited next, the others are pushed in slot order (popped LIFO). Selects
         // instead of branches: each divergent branch costs exec-mask and lane-mask
-        // bookkeeping on the scalar unit, which is as busy as the vector unit here.
-        const uint32_t valid = is_leaf ? 1u
-                                       : ((ch.x != -1 ? 1u : 0u) | (ch.y != -1 ? 2u : 0u) | (ch.z != -1 ? 4u : 0u) |
-                                          (ch.w != -1 ? 8u : 0u));
-        const uint32_t m = hm & valid;
-        const int32_t c01 = (m & 1u) ? ch.x : ch.y, c23 = (m & 4u) ? ch.z : ch.w;
-        next = m == 0 ? -1 : ((m & 3u) ? c01 : c23);
+        // bookkeeping on the scalar unit.
+        // (a leaf lane has slot 0 only: ch.x is its own ref, never -1)
+        const uint64_t m_inner = __builtin_amdgcn_ballot_w64(cur >= -1);
+        const uint64_t b0 = hit[0] & __builtin_amdgcn_ballot_w64(ch.x != -1),
+                       b1 = hit[1] & m_inner & __builtin_amdgcn_ballot_w64(ch.y != -1),
+                       b2 = hit[2] & m_inner & __builtin_amdgcn_ballot_w64(ch.z != -1),
+                       b3 = hit[3] & m_inner & __builtin_amdgcn_ballot_w64(ch.w != -1);
+        next = lane_of(b3) ? ch.w : -1;
+        next = lane_of(b2) ? ch.z : next;
+        next = lane_of(b1) ? ch.y : next;
+        next = lane_of(b0) ? ch.x : next;
         // A passed leaf re-test starts on the leaf's primitives. A leaf visited straight
         // after its parent re-tests the same f32 box with the same tMax (A10): the result
         // is known to be a hit, so its node load is skipped too (the visit is still counted).
@@ -489,10 +528,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
         // the other hit children, compacted in slot order, are written unconditionally to
         // ring positions sp..sp+2 (the ring keeps 3 free entries above sp); sp moves by
         // their count
-        const uint32_t rest = m & (m - 1u);  // bits 1..3 only
-        const int np_ = __builtin_popcount(rest);
-        const int32_t e0 = (rest & 2u) ? ch.y : ((rest & 4u) ? ch.z : ch.w);
-        const int32_t e1 = ((rest & 6u) == 6u) ? ch.z : ch.w;
+        // (slot i is pushed when it is hit and a lower slot is: slot 0 is never pushed)
+        const uint64_t r1 = b0 & b1, r2 = (b0 | b1) & b2, r3 = (b0 | b1 | b2) & b3;
+        const int np_ = (int)lane_of(r1) + (int)lane_of(r2) + (int)lane_of(r3);
+        const int32_t e0z = lane_of(r2) ? ch.z : ch.w;
+        const int32_t e0 = lane_of(r1) ? ch.y : e0z;
+        const int32_t e1 = lane_of(r1 & r2) ? ch.z : ch.w;
         stk[(sp & (S - 1)) * 256] = e0;
         stk[((sp + 1) & (S - 1)) * 256] = e1;
         stk[((sp + 2) & (S - 1)) * 256] = ch.w;
@@ -506,6 +547,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
 #endif
     // ---- advance: next child, else pop (bvh4.go:150-160), else the ray is done
     {
+      IZPI_MARK("advance");
       const bool do_pop = advance && next == -1 && sp > 0;
       const bool do_fin = advance && next == -1 && sp == 0;
       // the LDS read is unconditional (and volatile, so that the compiler keeps it a ds_read:
@@ -513,7 +555,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
       // drains every store)
       const int spn = sp - 1;
       int32_t top = *(volatile __attribute__((address_space(3))) int32_t*)&lds_stack[threadIdx.x + (spn & (S - 1)) * 256];
-      if (__ballot(do_pop && spn < low) != 0) {
+      if (any_spill && __ballot(do_pop && spn < low) != 0) {
         if (do_pop && spn < low) {
           top = gsp[(size_t)spn * spill_stride];
           low = spn;
@@ -524,7 +566,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
         __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) here, not for every pop
       }
       cur = (advance && next != -1) ? next : (do_pop ? top : cur);
-      sp = do_pop ? spn : sp;
+      sp = (advance && next == -1) ? spn : sp;  // a pop, or the ray is done: sp == -1, the lane is idle
       // An entry pushed after the last accepted hit meets the same tMax it was pushed
       // with, so a leaf's re-test against its (identical) box passes: skip the load.
       const bool lf = do_pop && ref_is_leaf(top) && spn >= clean_from && sc.leaf_shortcut;
