@@ -20,6 +20,7 @@
 
 #include "../../include/izpi_host.h"
 #include "gomath.h"
+#include "scene_pack.h"
 
 namespace {
 
@@ -290,26 +291,6 @@ struct Builder {
   }
 };
 
-// Upper bound on the traversal stack (bvh4.go:71-73): along any root-to-leaf path
-// a node pushes at most (valid children - 1) entries that stay below its subtree.
-uint32_t stack_bound(const std::vector<izpi_bvh4_node>& nodes) {
-  if (nodes.empty()) return 0;
-  std::vector<uint32_t> best(nodes.size(), 0);
-  for (size_t k = nodes.size(); k-- > 0;) {  // children have larger indices (pre-order)
-    const izpi_bvh4_node& n = nodes[k];
-    if (n.prim_count[0] > 0) { best[k] = 0; continue; }
-    uint32_t valid = 0, deepest = 0;
-    for (int i = 0; i < 4; i++) {
-      if (n.child[i] < 0) continue;
-      valid++;
-      uint32_t b = best[(size_t)n.child[i]];
-      if (b > deepest) deepest = b;
-    }
-    best[k] = (valid ? valid - 1 : 0) + deepest;
-  }
-  return best[0];
-}
-
 }  // namespace
 
 struct izpi_host_scene {
@@ -433,7 +414,7 @@ int izpi_host_build_scene_ex(const izpi_scene_input* in, uint32_t flags, izpi_ho
       uint32_t p = (uint32_t)prim_order[i];
       s->prim_ref[i] = p < nt ? IZPI_PRIM_REF(IZPI_PRIM_TRIANGLE, p) : IZPI_PRIM_REF(IZPI_PRIM_SPHERE, p - nt);
     }
-    s->stack_bound = stack_bound(s->nodes);
+    izpi_internal::stack_bound(s->nodes.data(), s->nodes.size(), &s->stack_bound);  // flatten: pre-order
   }
   // --- camera.New (camera.go:28-58) with aspect override (transport.go:522-529)
   izpi_scene_desc& d = s->desc;
@@ -505,7 +486,7 @@ int izpi_host_scene_set_bvh(izpi_host_scene* s, const izpi_bvh4_node* nodes, uin
     if (order[k] >= np || seen[order[k]]) { g_err = "order is not a permutation of the primitives"; return IZPI_ERR_INVALID; }
     seen[order[k]] = 1;
   }
-  for (uint32_t k = 0; k < num_nodes; k++) {  // children after parents (stack_bound's single backward pass)
+  for (uint32_t k = 0; k < num_nodes; k++) {  // children after parents (stack_bound's single backward pass, scene_pack.h)
     const izpi_bvh4_node& n = nodes[k];
     if (n.prim_count[0] > 0) {
       if (n.child[0] < 0 || (uint64_t)n.child[0] + (uint64_t)n.prim_count[0] > np) { g_err = "leaf range out of bounds"; return IZPI_ERR_INVALID; }
@@ -520,7 +501,7 @@ int izpi_host_scene_set_bvh(izpi_host_scene* s, const izpi_bvh4_node* nodes, uin
   s->nodes.assign(nodes, nodes + num_nodes);
   for (uint32_t k = 0; k < np; k++)
     s->prim_ref[k] = order[k] < nt ? IZPI_PRIM_REF(IZPI_PRIM_TRIANGLE, order[k]) : IZPI_PRIM_REF(IZPI_PRIM_SPHERE, order[k] - nt);
-  s->stack_bound = stack_bound(s->nodes);
+  izpi_internal::stack_bound(s->nodes.data(), s->nodes.size(), &s->stack_bound);  // children after parents: checked above
   s->desc.num_nodes = num_nodes;
   s->desc.nodes = s->nodes.data();
   s->desc.num_prims = np;

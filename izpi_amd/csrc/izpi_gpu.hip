@@ -3,6 +3,11 @@
 // post-processing and the component entries. The kernels of the hot path are in trace.hip and
 // shade.hip (izpi_kern.h).
 #include "izpi_kern.h"
+#include "scene_pack.h"
+
+using izpi_internal::Double4;
+using izpi_internal::pack_scene;
+using izpi_internal::PackedScene;
 
 // FireflyRejection (firefly_rejection.go:12-113) fused with XYZToRGB (rgb_image.go:28-67).
 // FireflyRejection reads only the ORIGINAL Y plane (it copies it first, :33-39) and
@@ -315,63 +320,6 @@ size_t carve_state(char* base, uint32_t slots, bool time, bool blk, bool cold, b
     if (b) b[k] = w;
   }
   return off;
-}
-
-// Quantise inner node g's child boxes (IZPI_SCENE_QUANTIZED_BVH) into q and replace g's
-// valid slot boxes by the decoded ones. Per axis: the origin is the minimum over the valid
-// children's mins, the scale 2^e the smallest for which every child's bounds, rounded
-// outwards to the grid, fit a byte; each rounded bound is then checked in the kernels' own
-// f32 decode (qdecode) and moved one step outwards while it would not contain the exact
-// bound. False when a valid bound is not finite or no exponent fits (the scene then keeps
-// its exact boxes).
-bool quantize_node(GInner& g, GInnerQ& q) {
-  memset(&q, 0, sizeof(q));
-  float* mn[3] = {g.mnx, g.mny, g.mnz};
-  float* mx[3] = {g.mxx, g.mxy, g.mxz};
-  for (int i = 0; i < 4; i++) q.child[i] = g.child[i];
-  for (int a = 0; a < 3; a++) {
-    float lo = 0.0f, hi = 0.0f;
-    bool any = false;
-    for (int i = 0; i < 4; i++) {
-      if (g.child[i] == -1) continue;
-      if (!std::isfinite(mn[a][i]) || !std::isfinite(mx[a][i])) return false;
-      lo = any ? std::min(lo, mn[a][i]) : mn[a][i];
-      hi = any ? std::max(hi, mx[a][i]) : mx[a][i];
-      any = true;
-    }
-    const double ext = (double)hi - (double)lo;
-    int e = -126;
-    if (ext > 0) e = std::max(-126, (int)std::ceil(std::log2(ext / 255.0)));
-    uint32_t qlo[4] = {0, 0, 0, 0}, qhi[4] = {0, 0, 0, 0};
-    for (;; e++) {
-      if (e > 127) return false;
-      const float sc = std::ldexp(1.0f, e);
-      bool ok = true;
-      for (int i = 0; i < 4 && ok; i++) {
-        if (g.child[i] == -1) continue;
-        double fl = std::floor(((double)mn[a][i] - (double)lo) / (double)sc);
-        int ql = (int)std::min(255.0, std::max(0.0, fl));
-        while (ql > 0 && qdecode(lo, (uint32_t)ql, sc) > mn[a][i]) ql--;  // qdecode(lo, 0) == lo <= every min
-        double fh = std::ceil(((double)mx[a][i] - (double)lo) / (double)sc);
-        int qh = (int)std::max((double)ql, std::min(256.0, fh));
-        while (qh <= 255 && qdecode(lo, (uint32_t)qh, sc) < mx[a][i]) qh++;
-        if (qh > 255) ok = false;
-        qlo[i] = (uint32_t)ql; qhi[i] = (uint32_t)qh;
-      }
-      if (ok) break;
-    }
-    const float sc = std::ldexp(1.0f, e);
-    q.org[a] = lo;
-    q.ex |= (uint32_t)(e + 127) << (8 * a);
-    for (int i = 0; i < 4; i++) {
-      q.q[a] |= qlo[i] << (8 * i);
-      q.q[3 + a] |= qhi[i] << (8 * i);
-      if (g.child[i] == -1) continue;
-      mn[a][i] = qdecode(lo, qlo[i], sc);
-      mx[a][i] = qdecode(lo, qhi[i], sc);
-    }
-  }
-  return true;
 }
 
 void free_scene(izpi_ctx* ctx) {
@@ -1018,6 +966,85 @@ int on_every_device(izpi_multi* m, F fn) {
     if (rcs[i]) { m->err = "device " + std::to_string(i) + ": " + m->ctx[i]->err; return rcs[i]; }
   return IZPI_OK;
 }
+
+static_assert(sizeof(Double4) == sizeof(double4), "PackedScene::mat_const uploads as DevScene::mat_const");
+
+// izpi_gpu_upload_scene's first steps: the context is idle on its device and holds no scene.
+int begin_upload(izpi_ctx* ctx, const izpi_scene_desc* d) {
+  if (!ctx || !d) return IZPI_ERR_INVALID;
+  // the scene descriptor is laid out alike in ABI 1 and 2
+  if (d->abi_version < 1 || d->abi_version > IZPI_ABI_VERSION) { ctx->err = "ABI version mismatch"; return IZPI_ERR_INVALID; }
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  free_scene(ctx);
+  return IZPI_OK;
+}
+
+// ... and its last: ps = pack_scene(d) becomes ctx's scene (after begin_upload). The
+// materials, the SPD tables and the camera go to the device as the descriptor has them.
+int upload_packed(izpi_ctx* ctx, const izpi_scene_desc* d, const PackedScene& ps) {
+  DevScene& sc = ctx->sc;
+  memset(&sc, 0, sizeof(sc));
+  GInner* di; GInnerQ* dq; GLeaf* dl; GPrim* dp; GShade* dsh; GTriVerts* dtv; GTriTex* dtt; GLight* dlt;
+  izpi_material* dm; Double4* dmc; MatTex* dmt; izpi_texture* dtx;
+  double *dtex, *dswl, *dsv;
+  UP(ps.inner.data(), ps.inner.size(), &di);
+  UP(ps.innerq.data(), ps.innerq.size(), &dq);
+  UP(ps.leaves.data(), ps.leaves.size(), &dl);
+  UP(ps.prims.data(), ps.prims.size(), &dp);
+  UP(ps.shade.data(), ps.shade.size(), &dsh);
+  UP(ps.triverts.data(), ps.triverts.size(), &dtv);
+  UP(ps.tritex.data(), ps.tritex.size(), &dtt);
+  UP(ps.lights.data(), ps.lights.size(), &dlt);
+  UP(d->materials, d->num_materials, &dm);
+  UP(ps.mat_const.data(), ps.mat_const.size(), &dmc);
+  UP(ps.mat_tex.data(), ps.mat_tex.size(), &dmt);
+  UP(ps.textures.data(), ps.textures.size(), &dtx);
+  UP(ps.texels.data(), ps.texels.size(), &dtex);
+  UP(d->spd_wavelengths, d->num_spd, &dswl);
+  UP(d->spd_values, d->num_spd, &dsv);
+#ifdef IZPI_SHADOW
+  {
+    GInner* si; GLeaf* sl; GPrim* sp;
+    UP(ps.inner.data(), ps.inner.size(), &si);
+    UP(ps.leaves.data(), ps.leaves.size(), &sl);
+    UP(ps.prims.data(), ps.prims.size(), &sp);
+    sc.sh_inner = si; sc.sh_leaves = sl; sc.sh_prims = sp;
+  }
+#endif
+  sc.inner = di; sc.innerq = dq; sc.leaves = dl; sc.prims = dp; sc.shade = dsh; sc.tritex = dtt; sc.lights = dlt;
+  sc.materials = dm; sc.mat_const = (const double4*)dmc; sc.mat_tex = dmt; sc.textures = dtx; sc.texels = dtex;
+  sc.spd_wl = dswl; sc.spd_val = dsv;
+  sc.root = ps.root; sc.num_inner = ps.num_inner; sc.num_prims = d->num_prims; sc.num_lights = d->num_lights;
+  sc.quantized = ps.quantized; sc.leaf_shortcut = ps.leaf_shortcut; sc.nan_free_bounds = ps.nan_free_bounds;
+  sc.tri_only = ps.tri_only; sc.time_free = ps.time_free; sc.no_pathlen = ps.no_pathlen;
+  sc.cam = d->camera;
+  ctx->d_triverts = dtv;
+  ctx->mat_ok_rgb = ps.mat_ok_rgb; ctx->mat_ok_spectral = ps.mat_ok_spectral;
+  ctx->basic_materials = ps.basic_materials; ctx->matset = ps.matset;
+  ctx->const_albedo = ps.const_albedo; ctx->any_uv = ps.any_uv;
+  ctx->pool_grow = 0;
+  ctx->stack_needed = ps.stack_needed;
+  ctx->num_prims = d->num_prims;
+  ctx->num_textures = d->num_textures;
+  ctx->num_materials = d->num_materials;
+  ctx->num_spd = d->num_spd;
+  ctx->have_scene = true;
+  ctx->sizing_valid = false;  // per-slot sizes depend on the scene
+  ctx->pv_sizing_valid = false;
+  // Load the code of the kernels this scene's renders run now, as part of the scene setup
+  // (izpi's Render timer starts after it, renderer.go:170): a first occupancy query loads a
+  // kernel's code object, 14 ms of a fresh renderer's first frame otherwise.
+  Tracer tr;
+  int rc = make_tracer(ctx, kDefaultTuning, !ctx->sc.tri_only || ctx->any_uv, &tr);
+  const bool compact = ctx->basic_materials && ctx->const_albedo;
+  if (!rc && ctx->mat_ok_rgb) rc = prepare_sampler<IZPI_SAMPLER_COLOUR, true>(ctx, compact);
+  if (!rc && ctx->mat_ok_rgb) rc = prepare_sampler<IZPI_SAMPLER_COLOUR, false>(ctx, compact);
+  if (!rc && ctx->mat_ok_spectral) rc = prepare_sampler<IZPI_SAMPLER_SPECTRAL, true>(ctx, false);
+  if (!rc && ctx->mat_ok_spectral) rc = prepare_sampler<IZPI_SAMPLER_SPECTRAL, false>(ctx, false);
+  if (!rc) rc = prepare_preview(ctx);
+  return rc;
+}
 }  // namespace
 
 extern "C" {
@@ -1074,421 +1101,11 @@ int izpi_gpu_close(izpi_ctx* ctx) {
 const char* izpi_gpu_last_error(izpi_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 
 int izpi_gpu_upload_scene(izpi_ctx* ctx, const izpi_scene_desc* d) {
-  if (!ctx || !d) return IZPI_ERR_INVALID;
-  // the scene descriptor is laid out alike in ABI 1 and 2
-  if (d->abi_version < 1 || d->abi_version > IZPI_ABI_VERSION) { ctx->err = "ABI version mismatch"; return IZPI_ERR_INVALID; }
-  HIP_TRY(hipSetDevice(ctx->device));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
-  free_scene(ctx);
-  const uint32_t nt = d->num_tris, ns = d->num_spheres;
-  // ---- BVH4: split reference nodes into inner nodes and leaf records
-  std::vector<int32_t> ref(d->num_nodes);
-  uint32_t n_inner = 0;
-  for (uint32_t k = 0; k < d->num_nodes; k++) {
-    const izpi_bvh4_node& n = d->nodes[k];
-    if (n.prim_count[0] > 0) {
-      for (int i = 1; i < 4; i++)
-        if (n.child[i] != -1) { ctx->err = "leaf node with more than one slot"; return IZPI_ERR_INVALID; }
-      const int32_t st = n.child[0], cnt = n.prim_count[0];
-      if (st < 0 || (uint64_t)st + (uint64_t)cnt > d->num_prims) { ctx->err = "leaf primitive range out of bounds"; return IZPI_ERR_INVALID; }
-      if (cnt > 7 || st >= (1 << 27)) { ctx->err = "leaf too large for the leaf-ref encoding"; return IZPI_ERR_UNSUPPORTED; }
-      ref[k] = make_leaf_ref(st, cnt);
-    } else {
-      for (int i = 0; i < 4; i++)
-        if (n.prim_count[i] != 0) { ctx->err = "inner node with a primitive slot"; return IZPI_ERR_INVALID; }
-      ref[k] = (int32_t)n_inner++;
-    }
-  }
-  std::vector<GInner> inner(std::max<uint32_t>(1, n_inner));  // >= 1: k_trace2's leaf lanes read a dummy inner node
-  std::vector<GLeaf> leaves(std::max<uint32_t>(1, d->num_prims));  // indexed by first primitive
-  uint32_t leaf_shortcut = 1;
-  for (uint32_t k = 0; k < d->num_nodes; k++) {
-    const izpi_bvh4_node& n = d->nodes[k];
-    if (ref[k] <= -2) {
-      GLeaf& L = leaves[(size_t)leaf_start(ref[k])];
-      L.mn[0] = n.min_x[0]; L.mn[1] = n.min_y[0]; L.mn[2] = n.min_z[0];
-      L.mx[0] = n.max_x[0]; L.mx[1] = n.max_y[0]; L.mx[2] = n.max_z[0];
-      L.start = n.child[0]; L.count = n.prim_count[0];
-    } else {
-      GInner& g = inner[(size_t)ref[k]];
-      memcpy(g.mnx, n.min_x, 16); memcpy(g.mny, n.min_y, 16); memcpy(g.mnz, n.min_z, 16);
-      memcpy(g.mxx, n.max_x, 16); memcpy(g.mxy, n.max_y, 16); memcpy(g.mxz, n.max_z, 16);
-      for (int i = 0; i < 4; i++) {
-        int32_t c = n.child[i];
-        if (c != -1 && (c < 0 || (uint32_t)c >= d->num_nodes)) { ctx->err = "child index out of bounds"; return IZPI_ERR_INVALID; }
-        g.child[i] = c == -1 ? -1 : ref[(size_t)c];
-        g.pad[i] = 0;
-        if (c >= 0 && ref[(size_t)c] <= -2) {
-          // a leaf's re-test (A10) may be skipped only if its slot-0 box is bit-identical
-          // to this slot's box (flattenBVH4 converts the same node.box twice, bvh4.go:745-781)
-          const izpi_bvh4_node& lnode = d->nodes[(size_t)c];
-          const float pb[6] = {n.min_x[i], n.min_y[i], n.min_z[i], n.max_x[i], n.max_y[i], n.max_z[i]};
-          const float lb[6] = {lnode.min_x[0], lnode.min_y[0], lnode.min_z[0], lnode.max_x[0], lnode.max_y[0], lnode.max_z[0]};
-          if (memcmp(pb, lb, sizeof(pb)) != 0) leaf_shortcut = 0;
-        }
-      }
-    }
-  }
-  // ---- quantised child boxes (IZPI_SCENE_QUANTIZED_BVH, ABI 3): `inner` and the leaf
-  // records take the decoded boxes, which every traversal instance then tests (the 64-B
-  // nodes and the 128-B ones describe the same tree); a leaf's re-test box is its decoded
-  // parent slot, so its shortcut holds
-  std::vector<GInnerQ> innerq;
-  bool quantized = false;
-  if (d->abi_version >= 3 && (d->flags & IZPI_SCENE_QUANTIZED_BVH) && n_inner > 0) {
-    std::vector<GInner> dec(inner);
-    innerq.resize(n_inner);
-    quantized = true;
-    for (uint32_t k = 0; k < n_inner && quantized; k++) quantized = quantize_node(dec[k], innerq[k]);
-    if (quantized) {
-      inner.swap(dec);
-      for (uint32_t k = 0; k < n_inner; k++) {
-        const GInner& g = inner[k];
-        for (int i = 0; i < 4; i++) {
-          if (!ref_is_leaf(g.child[i])) continue;
-          GLeaf& L = leaves[(size_t)leaf_start(g.child[i])];
-          L.mn[0] = g.mnx[i]; L.mn[1] = g.mny[i]; L.mn[2] = g.mnz[i];
-          L.mx[0] = g.mxx[i]; L.mx[1] = g.mxy[i]; L.mx[2] = g.mxz[i];
-        }
-      }
-      leaf_shortcut = 1;
-    } else {
-      innerq.clear();
-    }
-  }
-  // ---- primitives in leaf order
-  std::vector<GPrim> prims(d->num_prims);
-  std::vector<GShade> shade(d->num_prims);
-  for (uint32_t k = 0; k < d->num_prims; k++) {
-    const uint32_t r = d->prim_ref[k], kind = IZPI_PRIM_KIND(r), idx = IZPI_PRIM_INDEX(r);
-    GPrim& g = prims[k];
-    g.kind = kind; g.index = idx;
-    GShade& gs = shade[k];
-    memset(&gs, 0, sizeof(gs));
-    gs.ref = r;
-    if (kind == IZPI_PRIM_TRIANGLE) {
-      if (idx >= nt) { ctx->err = "triangle ref out of range"; return IZPI_ERR_INVALID; }
-      memcpy(gs.n, d->tri_normal + 3 * (size_t)idx, 24);
-      gs.mk = d->tri_mat[idx];
-      memcpy(g.a, d->tri_v0 + 3 * (size_t)idx, 24); memcpy(g.a + 3, d->tri_e1 + 3 * (size_t)idx, 24);
-      memcpy(g.a + 6, d->tri_e2 + 3 * (size_t)idx, 24);
-    } else {
-      if (idx >= ns) { ctx->err = "sphere ref out of range"; return IZPI_ERR_INVALID; }
-      gs.mk = d->sph_mat[idx];
-      memcpy(g.a, d->sph_center0 + 3 * (size_t)idx, 24); memcpy(g.a + 3, d->sph_center1 + 3 * (size_t)idx, 24);
-      g.a[6] = d->sph_radius[idx]; g.a[7] = d->sph_time[2 * (size_t)idx]; g.a[8] = d->sph_time[2 * (size_t)idx + 1];
-    }
-  }
-  // ---- lights
-  std::vector<GLight> lights(d->num_lights);
-  for (uint32_t i = 0; i < d->num_lights; i++) {
-    GLight& L = lights[i];
-    memset(&L, 0, sizeof(L));
-    const uint32_t r = d->light_ref[i], kind = IZPI_PRIM_KIND(r), idx = IZPI_PRIM_INDEX(r);
-    L.kind = kind; L.index = idx;
-    if (kind == IZPI_PRIM_TRIANGLE) {
-      if (idx >= nt) { ctx->err = "light triangle out of range"; return IZPI_ERR_INVALID; }
-      const izpi_material& m = d->materials[d->tri_mat[idx]];
-      if (m.kind == IZPI_MAT_PBR && m.normal_tex >= 0) { ctx->err = "normal-mapped light"; return IZPI_ERR_UNSUPPORTED; }
-      memcpy(L.v0, d->tri_v0 + 3 * (size_t)idx, 24); memcpy(L.v1, d->tri_v1 + 3 * (size_t)idx, 24);
-      memcpy(L.v2, d->tri_v2 + 3 * (size_t)idx, 24); memcpy(L.e1, d->tri_e1 + 3 * (size_t)idx, 24);
-      memcpy(L.e2, d->tri_e2 + 3 * (size_t)idx, 24); memcpy(L.n, d->tri_normal + 3 * (size_t)idx, 24);
-      L.area = d->tri_area[idx];
-    } else {
-      if (idx >= ns) { ctx->err = "light sphere out of range"; return IZPI_ERR_INVALID; }
-      memcpy(L.c0, d->sph_center0 + 3 * (size_t)idx, 24); memcpy(L.c1, d->sph_center1 + 3 * (size_t)idx, 24);
-      L.radius = d->sph_radius[idx]; L.t0 = d->sph_time[2 * (size_t)idx]; L.t1 = d->sph_time[2 * (size_t)idx + 1];
-      // Sphere.center(0) (sphere.go:125-127) with the device's operation order:
-      // c0 + (c1 - c0) * ((0 - t0) / (t1 - t0)), computed once here
-      const double k = (0.0 - L.t0) / (L.t1 - L.t0);
-      for (int q = 0; q < 3; q++) L.cz[q] = L.c0[q] + (L.c1[q] - L.c0[q]) * k;
-    }
-  }
-  // ---- material flags: bit0 a texture of the material reads (u,v); bit1 usable by
-  // the Colour sampler; bit2 usable by the Spectral sampler (the reference would
-  // dereference a nil texture otherwise).
-  std::vector<uint32_t> mflags(d->num_materials, 0);
-  ctx->mat_ok_rgb = ctx->mat_ok_spectral = true;
-  ctx->basic_materials = true;
-  ctx->matset = 0;
-  ctx->pool_grow = 0;
-  for (uint32_t i = 0; i < d->num_materials; i++) {
-    const izpi_material& m = d->materials[i];
-    const int32_t ids[] = {m.albedo_tex, m.spectral_tex, m.normal_tex, m.roughness_tex, m.metalness_tex, m.absorb_tex};
-    for (int32_t t : ids) {
-      if (t < -1 || t >= (int32_t)d->num_textures) { ctx->err = "texture index out of range"; return IZPI_ERR_INVALID; }
-      if (t >= 0 && (d->textures[t].kind == IZPI_TEX_IMAGE || d->textures[t].kind == IZPI_TEX_SPECTRAL_IMAGE)) mflags[i] |= 1u;
-    }
-    // a SpectralImage is made for PBR albedos (transport.go:486-497) and reads the hit's
-    // (u, v): Lambert / DiffuseLight / PBR spectral textures only
-    for (int32_t t : {m.normal_tex, m.roughness_tex, m.metalness_tex, m.absorb_tex, m.albedo_tex})
-      if (t >= 0 && d->textures[t].kind == IZPI_TEX_SPECTRAL_IMAGE) { ctx->err = "SpectralImage outside a spectral albedo"; return IZPI_ERR_INVALID; }
-    if (m.spectral_tex >= 0 && d->textures[m.spectral_tex].kind == IZPI_TEX_SPECTRAL_IMAGE && m.kind != IZPI_MAT_LAMBERT &&
-        m.kind != IZPI_MAT_DIFFUSE_LIGHT && m.kind != IZPI_MAT_PBR) {
-      ctx->err = "SpectralImage outside a spectral albedo";
-      return IZPI_ERR_INVALID;
-    }
-    auto is_rgb = [&](int32_t t) { return t >= 0 && (d->textures[t].kind == IZPI_TEX_CONSTANT || d->textures[t].kind == IZPI_TEX_IMAGE); };
-    auto is_spec = [&](int32_t t) {
-      return t >= 0 && (d->textures[t].kind == IZPI_TEX_SPECTRAL_GAUSSIAN || d->textures[t].kind == IZPI_TEX_SPECTRAL_TABULATED ||
-                        d->textures[t].kind == IZPI_TEX_SPECTRAL_IMAGE);
-    };
-    auto opt_rgb = [&](int32_t t) { return t == -1 || is_rgb(t); };
-    bool rgb = false, spec = false;
-    switch (m.kind) {
-      case IZPI_MAT_LAMBERT: case IZPI_MAT_DIFFUSE_LIGHT: rgb = is_rgb(m.albedo_tex); spec = is_spec(m.spectral_tex); break;
-      case IZPI_MAT_DIELECTRIC: rgb = true; spec = is_spec(m.spectral_tex) && (m.absorb_tex == -1 || is_spec(m.absorb_tex)); break;
-      case IZPI_MAT_METAL: rgb = spec = true; break;
-      case IZPI_MAT_ISOTROPIC: rgb = spec = is_rgb(m.albedo_tex); break;  // SpectralScatter reads the RGB albedo's X
-      case IZPI_MAT_PBR: {
-        bool aux = opt_rgb(m.normal_tex) && opt_rgb(m.roughness_tex) && opt_rgb(m.metalness_tex);
-        rgb = aux && is_rgb(m.albedo_tex);
-        spec = aux && (is_spec(m.spectral_tex) || is_rgb(m.albedo_tex));
-        break;
-      }
-      default: ctx->err = "unknown material kind"; return IZPI_ERR_INVALID;
-    }
-    if (m.kind != IZPI_MAT_LAMBERT && m.kind != IZPI_MAT_DIFFUSE_LIGHT) ctx->basic_materials = false;
-    ctx->matset |= m.kind == IZPI_MAT_DIELECTRIC ? MS_DIEL : m.kind == IZPI_MAT_METAL ? MS_METAL
-                 : m.kind == IZPI_MAT_PBR ? MS_PBR : m.kind == IZPI_MAT_ISOTROPIC ? MS_ISO : 0u;
-    if (rgb) mflags[i] |= 2u; else ctx->mat_ok_rgb = false;
-    if (spec) mflags[i] |= 4u; else ctx->mat_ok_spectral = false;
-  }
-  // ---- material essentials in the per-primitive shade records
-  // (gs.mk holds the bare material index until here)
-  if (d->num_materials >= (1u << 24)) { ctx->err = "too many materials"; return IZPI_ERR_INVALID; }
-  std::vector<double4> mconst(std::max<uint32_t>(1, d->num_materials), make_double4(0, 0, 0, 0));
-  std::vector<uint32_t> mcflags(d->num_materials, 0);
-  for (uint32_t i = 0; i < d->num_materials; i++) {
-    const izpi_material& m = d->materials[i];
-    mcflags[i] = (mflags[i] & 1u) ? 2u : 0u;
-    if ((m.kind == IZPI_MAT_LAMBERT || m.kind == IZPI_MAT_DIFFUSE_LIGHT) && m.albedo_tex >= 0 &&
-        d->textures[m.albedo_tex].kind == IZPI_TEX_CONSTANT) {
-      const double* v = d->textures[m.albedo_tex].value;
-      mconst[i] = make_double4(v[0], v[1], v[2], 0.0);
-      mcflags[i] |= 1u;
-    }
-  }
-  ctx->const_albedo = true;
-  ctx->any_uv = false;
-  for (uint32_t i = 0; i < d->num_materials; i++)
-    if (mflags[i] & 1u) ctx->any_uv = true;
-  for (uint32_t i = 0; i < d->num_materials; i++)
-    if ((d->materials[i].kind == IZPI_MAT_LAMBERT || d->materials[i].kind == IZPI_MAT_DIFFUSE_LIGHT) && !(mcflags[i] & 1u))
-      ctx->const_albedo = false;
-  for (GShade& gs : shade) {
-    const uint32_t mat = gs.mk;
-    if (mat >= d->num_materials) { ctx->err = "material index out of range"; return IZPI_ERR_INVALID; }
-    if (d->materials[mat].kind >= 64u) { ctx->err = "unknown material kind"; return IZPI_ERR_INVALID; }
-    gs.mk = mat << 8 | d->materials[mat].kind << 2 | mcflags[mat];
-  }
-  // ---- upload
-  DevScene& sc = ctx->sc;
-  memset(&sc, 0, sizeof(sc));
-  GInner* di; GLeaf* dl; GPrim* dp; GShade* dsh; GLight* dlt; GTriTex* dtt = nullptr;
-  double *dtex, *dswl, *dsv;
-  izpi_material* dm; izpi_texture* dtx;
-  UP(inner.data(), inner.size(), &di);
-  GInnerQ* dq = nullptr;
-  if (quantized) UP(innerq.data(), innerq.size(), &dq);
-  UP(leaves.data(), leaves.size(), &dl);
-  UP(prims.data(), prims.size(), &dp);
-  UP(shade.data(), shade.size(), &dsh);
-  {  // the triangles' v1, v2 in leaf order (Triangle.HitEdge's sides: the WireFrame sampler)
-    std::vector<GTriVerts> tv(std::max<uint32_t>(1, d->num_prims));
-    memset(tv.data(), 0, tv.size() * sizeof(GTriVerts));
-    for (uint32_t k = 0; k < d->num_prims; k++) {
-      const uint32_t r = d->prim_ref[k];
-      if (IZPI_PRIM_KIND(r) != IZPI_PRIM_TRIANGLE) continue;
-      memcpy(tv[k].v1, d->tri_v1 + 3 * (size_t)IZPI_PRIM_INDEX(r), 24);
-      memcpy(tv[k].v2, d->tri_v2 + 3 * (size_t)IZPI_PRIM_INDEX(r), 24);
-    }
-    GTriVerts* dtv;
-    UP(tv.data(), tv.size(), &dtv);
-    ctx->d_triverts = dtv;
-  }
-  for (uint32_t i = 0; i < d->num_materials; i++)
-    if (d->materials[i].kind == IZPI_MAT_PBR && d->materials[i].normal_tex >= 0 && nt && (!d->tri_tangent || !d->tri_bitangent)) {
-      ctx->err = "a PBR normal map needs the triangles' tangents and bitangents";
-      return IZPI_ERR_INVALID;
-    }
-  // triangle UVs and tangent frames in leaf order (shading reads them for image textures
-  // and normal maps; izpi_gpu_trace's hit records carry the UVs)
-  if (d->num_prims && (d->tri_uv || d->tri_tangent || d->tri_bitangent)) {
-    std::vector<GTriTex> tt(d->num_prims);
-    for (uint32_t k = 0; k < d->num_prims; k++) {
-      memset(&tt[k], 0, sizeof(GTriTex));
-      const uint32_t r = d->prim_ref[k];
-      if (IZPI_PRIM_KIND(r) != IZPI_PRIM_TRIANGLE) continue;
-      const size_t ti = IZPI_PRIM_INDEX(r);
-      if (d->tri_uv) memcpy(tt[k].uv, d->tri_uv + 6 * ti, 48);
-      if (d->tri_tangent) memcpy(tt[k].tg, d->tri_tangent + 3 * ti, 24);
-      if (d->tri_bitangent) memcpy(tt[k].bt, d->tri_bitangent + 3 * ti, 24);
-    }
-    UP(tt.data(), tt.size(), &dtt);
-  }
-  UP(lights.data(), lights.size(), &dlt);
-  UP(d->materials, d->num_materials, &dm);
-  double4* dmc;
-  UP(mconst.data(), mconst.size(), &dmc);
-  for (uint32_t i = 0; i < d->num_textures; i++) {
-    const izpi_texture& t = d->textures[i];
-    if (t.kind != IZPI_TEX_IMAGE && t.kind != IZPI_TEX_SPECTRAL_IMAGE) continue;
-    if (t.width == 0 || t.height == 0 || t.texel_offset + 4ull * t.width * t.height > d->num_texels || !d->texels) {
-      ctx->err = "image texture outside the texel array";
-      return IZPI_ERR_INVALID;
-    }
-  }
-  // device copy of the textures: pad0 = 1 marks a tabulated SPD with non-decreasing
-  // wavelengths, which tex_spectral searches by bisection; pad0 = 2 one whose wavelengths
-  // are also near-uniform (entry j within half a step of wl[0] + j * step), whose interval
-  // tex_spectral guesses from lambda with value[0] = wl[0] and value[1] = 1 / step
-  std::vector<izpi_texture> texs(d->textures, d->textures + d->num_textures);
-  for (izpi_texture& t : texs) {
-    t.pad0 = 0;
-    if (t.kind != IZPI_TEX_SPECTRAL_TABULATED || t.spd_count < 2) continue;  // n = 1: the scan returns 0.0
-    if ((uint64_t)t.spd_offset + t.spd_count > d->num_spd) { ctx->err = "SPD range out of bounds"; return IZPI_ERR_INVALID; }
-    const double* wl = d->spd_wavelengths + t.spd_offset;
-    const uint32_t n = t.spd_count;
-    bool sorted = true;
-    for (uint32_t i = 1; i < n; i++)
-      if (!(wl[i - 1] <= wl[i])) sorted = false;
-    t.pad0 = sorted ? 1u : 0u;
-    const double span = wl[n - 1] - wl[0];
-    if (!sorted || !(span > 0) || !std::isfinite(span)) continue;
-    const double scale = (double)(n - 1) / span;
-    bool uniform = std::isfinite(scale);
-    for (uint32_t i = 0; i < n && uniform; i++)
-      if (!(std::fabs((wl[i] - wl[0]) * scale - (double)i) <= 0.5)) uniform = false;
-    if (uniform) { t.pad0 = 2; t.value[0] = wl[0]; t.value[1] = scale; }
-  }
-  // texels in their device storage form (TexSlot): every image texture gets its own run,
-  // RGBA runs 32-B aligned; a texture whose R, G and B are bit-identical in every texel is
-  // stored as one double per texel
-  std::vector<double> texels;
-  std::vector<uint32_t> tex_fmt(d->num_textures, TEXF_OTHER);
-  for (uint32_t i = 0; i < d->num_textures; i++) {
-    izpi_texture& t = texs[i];
-    if (t.kind != IZPI_TEX_IMAGE && t.kind != IZPI_TEX_SPECTRAL_IMAGE) continue;
-    const double* src = d->texels + t.texel_offset;
-    const uint64_t np = (uint64_t)t.width * t.height;
-    bool gray = t.kind == IZPI_TEX_IMAGE;
-    for (uint64_t k = 0; k < np && gray; k++)
-      gray = memcmp(src + 4 * k, src + 4 * k + 1, 8) == 0 && memcmp(src + 4 * k, src + 4 * k + 2, 8) == 0;
-    texels.resize((texels.size() + 3) & ~(size_t)3);
-    t.texel_offset = texels.size();
-    if (gray) {
-      for (uint64_t k = 0; k < np; k++) texels.push_back(src[4 * k]);
-    } else {
-      texels.insert(texels.end(), src, src + 4 * np);
-    }
-    if (t.kind == IZPI_TEX_IMAGE) t.pad0 = tex_fmt[i] = gray ? TEXF_GRAY : TEXF_RGBA;
-  }
-  // the materials' texture slots (albedo, normal, roughness, metalness)
-  std::vector<MatTex> mtex(std::max<uint32_t>(1, d->num_materials));
-  for (uint32_t i = 0; i < d->num_materials; i++) {
-    const izpi_material& m = d->materials[i];
-    const int32_t ids[4] = {m.albedo_tex, m.normal_tex, m.roughness_tex, m.metalness_tex};
-    for (int k = 0; k < 4; k++) {
-      TexSlot& sl = mtex[i].s[k];
-      const int32_t id = ids[k];
-      if (id < 0) { sl.off = 0; sl.w = 0; sl.hf = (uint32_t)TEXF_NONE << 30; continue; }
-      const izpi_texture& t = texs[id];
-      if (tex_fmt[id] <= TEXF_GRAY && t.height < (1u << 30)) {
-        sl.off = t.texel_offset; sl.w = t.width; sl.hf = t.height | tex_fmt[id] << 30;
-      } else {
-        sl.off = (uint64_t)id; sl.w = 0; sl.hf = (uint32_t)TEXF_OTHER << 30;
-      }
-    }
-  }
-  MatTex* dmt;
-  UP(mtex.data(), mtex.size(), &dmt);
-  UP(texs.data(), d->num_textures, &dtx);
-  if (texels.empty()) texels.push_back(0.0);
-  UP(texels.data(), texels.size(), &dtex);
-  UP(d->spd_wavelengths, d->num_spd, &dswl);
-  UP(d->spd_values, d->num_spd, &dsv);
-  sc.num_inner = n_inner; sc.num_prims = d->num_prims;
-#ifdef IZPI_SHADOW
-  {
-    GInner* si; GLeaf* sl; GPrim* sp;
-    UP(inner.data(), inner.size(), &si);
-    UP(leaves.data(), leaves.size(), &sl);
-    UP(prims.data(), prims.size(), &sp);
-    sc.sh_inner = si; sc.sh_leaves = sl; sc.sh_prims = sp;
-  }
-#endif
-  sc.inner = di; sc.innerq = dq; sc.quantized = quantized ? 1u : 0u; sc.leaves = dl; sc.prims = dp; sc.shade = dsh; sc.tritex = dtt; sc.lights = dlt; sc.materials = dm;
-  sc.mat_const = dmc; sc.mat_tex = dmt; sc.textures = dtx; sc.texels = dtex; sc.spd_wl = dswl; sc.spd_val = dsv;
-  sc.root = d->num_nodes ? ref[0] : -1;
-  sc.num_lights = d->num_lights;
-  sc.tri_only = d->num_spheres == 0 ? 1u : 0u;
-  {  // time_free: no sphere moves, so Sphere.center(time) == center(time0) for every ray time
-     // (c1 == c0 finite: (c1 - c0) * x = +0 for the x >= 0 every camera time gives)
-    bool tf = true;
-    const double tmin_cam = std::min(d->camera.time0, d->camera.time1);
-    if (!std::isfinite(d->camera.time0) || !std::isfinite(d->camera.time1)) tf = false;
-    for (uint32_t i = 0; tf && i < d->num_spheres; i++) {
-      const double* c0 = d->sph_center0 + 3 * (size_t)i;
-      const double* c1 = d->sph_center1 + 3 * (size_t)i;
-      const double t0 = d->sph_time[2 * (size_t)i], t1 = d->sph_time[2 * (size_t)i + 1];
-      for (int k = 0; k < 3; k++)
-        if (!std::isfinite(c0[k]) || memcmp(c0 + k, c1 + k, sizeof(double)) != 0) tf = false;
-      if (!std::isfinite(t0) || !std::isfinite(t1) || !(t1 > t0) || !(tmin_cam >= t0)) tf = false;
-    }
-    sc.time_free = tf ? 1u : 0u;
-  }
-  sc.no_pathlen = 1;
-  for (uint32_t i = 0; i < d->num_materials; i++)
-    if (d->materials[i].kind == IZPI_MAT_DIELECTRIC) sc.no_pathlen = 0;
-  sc.leaf_shortcut = leaf_shortcut;
-  sc.nan_free_bounds = 1;
-  for (const GInner& g : inner) {
-    const float* f = g.mnx;  // the 24 bounds are contiguous
-    for (int i = 0; i < 24; i++) if (f[i] != f[i]) sc.nan_free_bounds = 0;
-  }
-  for (const GLeaf& L : leaves)  // leaf re-tests run through the same 4-slot test
-    for (int i = 0; i < 3; i++) if (L.mn[i] != L.mn[i] || L.mx[i] != L.mx[i]) sc.nan_free_bounds = 0;
-  sc.cam = d->camera;
-  // traversal stack bound (see host_scene.cpp stack_bound)
-  {
-    std::vector<uint32_t> best(d->num_nodes, 0);
-    for (size_t k = d->num_nodes; k-- > 0;) {
-      const izpi_bvh4_node& n = d->nodes[k];
-      if (n.prim_count[0] > 0) continue;
-      uint32_t valid = 0, deepest = 0;
-      for (int i = 0; i < 4; i++) {
-        if (n.child[i] < 0) continue;
-        valid++;
-        if ((uint32_t)n.child[i] <= k) { ctx->err = "BVH4 nodes not in pre-order"; return IZPI_ERR_INVALID; }
-        deepest = std::max(deepest, best[(size_t)n.child[i]]);
-      }
-      best[k] = (valid ? valid - 1 : 0) + deepest;
-    }
-    ctx->stack_needed = d->num_nodes ? best[0] : 0;
-    ctx->num_prims = d->num_prims;
-  }
-  ctx->have_scene = true;
-  ctx->sizing_valid = false;  // per-slot sizes depend on the scene
-  ctx->pv_sizing_valid = false;
-  ctx->num_textures = d->num_textures;
-  ctx->num_materials = d->num_materials;
-  ctx->num_spd = d->num_spd;
-  // Load the code of the kernels this scene's renders run now, as part of the scene setup
-  // (izpi's Render timer starts after it, renderer.go:170): a first occupancy query loads a
-  // kernel's code object, 14 ms of a fresh renderer's first frame otherwise.
-  {
-    Tracer tr;
-    int rc = make_tracer(ctx, kDefaultTuning, !ctx->sc.tri_only || ctx->any_uv, &tr);
-    const bool compact = ctx->basic_materials && ctx->const_albedo;
-    if (!rc && ctx->mat_ok_rgb) rc = prepare_sampler<IZPI_SAMPLER_COLOUR, true>(ctx, compact);
-    if (!rc && ctx->mat_ok_rgb) rc = prepare_sampler<IZPI_SAMPLER_COLOUR, false>(ctx, compact);
-    if (!rc && ctx->mat_ok_spectral) rc = prepare_sampler<IZPI_SAMPLER_SPECTRAL, true>(ctx, false);
-    if (!rc && ctx->mat_ok_spectral) rc = prepare_sampler<IZPI_SAMPLER_SPECTRAL, false>(ctx, false);
-    if (!rc) rc = prepare_preview(ctx);
-    if (rc) return rc;
-  }
-  return IZPI_OK;
+  int rc = begin_upload(ctx, d);
+  if (rc) return rc;
+  PackedScene ps;
+  rc = pack_scene(d, &ps, &ctx->err);
+  return rc ? rc : upload_packed(ctx, d, ps);
 }
 
 uint64_t izpi_gpu_output_bytes(const izpi_render_req* req) {
@@ -1777,10 +1394,14 @@ izpi_ctx* izpi_gpu_multi_context(izpi_multi* m, uint32_t i) { return (m && i < m
 
 int izpi_gpu_multi_upload_scene(izpi_multi* m, const izpi_scene_desc* scene) {
   if (!m) return IZPI_ERR_INVALID;
-  for (size_t i = 0; i < m->ctx.size(); i++) {  // the scene is replicated per GPU
-    const int rc = izpi_gpu_upload_scene(m->ctx[i], scene);
+  PackedScene ps;  // packed once (after the first context's checks); replicated per GPU
+  for (size_t i = 0; i < m->ctx.size(); i++) {
+    izpi_ctx* c = m->ctx[i];
+    int rc = begin_upload(c, scene);
+    if (!rc && i == 0) rc = pack_scene(scene, &ps, &c->err);
+    if (!rc) rc = upload_packed(c, scene, ps);
     if (rc) {
-      m->err = "device " + std::to_string(i) + ": " + m->ctx[i]->err;
+      m->err = "device " + std::to_string(i) + ": " + c->err;
       return rc;
     }
   }

@@ -944,7 +944,7 @@ struct ShadeParams {
 // Metal/PBR scenes (C4: shading -2% against MATSET_FULL). A Lambert/light/dielectric
 // instance measured 3% SLOWER than MATSET_FULL on C5 (its register allocation came out
 // worse), so dielectric scenes run MATSET_FULL.
-enum { MS_DIEL = 1, MS_METAL = 2, MS_PBR = 4, MS_ISO = 8, MS_CONST = 16 };
+// (the MS_* feature bits: scene_records.h)
 enum {
   MATSET_BASIC = 0,
   MATSET_SURF = MS_METAL | MS_PBR,

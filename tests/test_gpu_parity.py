@@ -172,6 +172,36 @@ def test_render_c1_bitwise(gpu):
     r.close()
 
 
+def test_refused_scene_leaves_no_scene_and_the_next_upload_is_whole(gpu):
+    """A descriptor the packer refuses (scene_pack.cpp): the upload returns its status and
+    text, the context has no scene, and the valid scene uploaded again renders the first
+    upload's canvas in the same scene bytes. izpi_gpu_multi_upload_scene names the device."""
+    L = N.lib()
+    cfg = configs.configs()["C1"]
+    r = GPURenderer(cfg.build(), cfg.width, cfg.height, 2, sampler=cfg.sampler)
+    img = r.render()
+    scene_bytes = r.stats["scene_bytes"]
+    good = r.host.desc
+    bad = N.SceneDesc.from_buffer_copy(good)
+    refs = (C.c_uint32 * good.num_prims)(*good.prim_ref[:good.num_prims])
+    refs[good.num_prims // 2] = N.prim_ref(0, good.num_tris)  # (kind 0: a triangle)
+    bad.prim_ref = C.cast(refs, type(bad.prim_ref))
+    assert L.izpi_gpu_upload_scene(r.ctx, C.byref(bad)) == N.IZPI_ERR_INVALID
+    assert L.izpi_gpu_last_error(r.ctx) == b"triangle ref out of range"
+    req = r.request()
+    canvas = np.zeros((cfg.height, cfg.width, 4))
+    assert L.izpi_gpu_render(r.ctx, C.byref(req), canvas.ctypes.data_as(C.POINTER(C.c_double)), None) == N.IZPI_ERR_NO_SCENE
+    assert L.izpi_gpu_upload_scene(r.ctx, C.byref(good)) == 0, L.izpi_gpu_last_error(r.ctx)
+    again = r.render()
+    assert again.tobytes() == img.tobytes() and r.stats["scene_bytes"] == scene_bytes
+    r.close()
+    m = C.c_void_p()
+    assert L.izpi_gpu_multi_open((C.c_int * 1)(0), 1, C.byref(m)) == 0
+    assert L.izpi_gpu_multi_upload_scene(m, C.byref(bad)) == N.IZPI_ERR_INVALID
+    assert L.izpi_gpu_multi_last_error(m) == b"device 0: triangle ref out of range"
+    L.izpi_gpu_multi_close(m)
+
+
 def test_render_dragon_small_bitwise(gpu):
     scene = configs.cornell_dragon(1.0, n=60)
     r = GPURenderer(scene, 64, 64, 8)
