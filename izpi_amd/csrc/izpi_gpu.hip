@@ -571,6 +571,9 @@ int render_body(izpi_ctx* ctx, const izpi_render_req* req, double* out_dev) {
   const double t_tiles = host_ms();
   int trc = make_tracer(ctx, tu, !ctx->sc.tri_only || ctx->any_uv, &tr);
   if (trc) return trc;
+  if (tu.flags & IZPI_TUNE_PASS_LOG)  // diagnostics: the k_trace2 instance this render runs
+    fprintf(stderr, "IZPI_TRACE_INSTANCE dist=%d tri=%d lds_bvh=%d ray_lds=%d q=%d\n", (int)tr.p2, (int)tr.tri, (int)tr.lds_bvh,
+            (int)tr.ray_lds, (int)tr.qnodes);
   const double t_tracer = host_ms();
   if (preview) return preview_body(ctx, req, sc, tr, tu, tiles, tw, th, num_pixels, out_dev);
   // Sizing against the HBM this context may use: what is free plus the render buffers it
@@ -753,6 +756,8 @@ int render_body(izpi_ctx* ctx, const izpi_render_req* req, double* out_dev) {
     sp.prims_staged = 0;
   // k_shade / k_tail's LDS arena: the prefix of lds_off's layout that this render stages
   sc.lds_bytes = sp.prims_staged ? lds_off::END : sp.staged == 2 ? lds_off::SPECTRAL_END : sp.staged ? lds_off::COLOUR_END : 0;
+  if (tu.flags & IZPI_TUNE_PASS_LOG)  // diagnostics: which tables this render's k_shade / k_tail blocks copy into LDS
+    fprintf(stderr, "IZPI_SHADE_TABLES tables=%u prims=%u lds_bytes=%u\n", sp.staged, sp.prims_staged, sc.lds_bytes);
   sp.pool = rec_pool ? ctx->d_pool : nullptr; sp.pool_ring = rec_pool ? ctx->d_ring : nullptr;
   sp.pool_ctr = rec_pool ? ctx->d_pool_ctr : nullptr;
   sp.counters = ctx->d_counters; sp.cpart = ctx->d_cpart; sp.error = misc(ctx, 1);

@@ -15,6 +15,7 @@ from izpi_amd import _native as N
 from izpi_amd import configs
 from izpi_amd.renderer import GPURenderer, common_tiles
 from oracle import oracle as O
+from tests.table_cases import log_line
 
 pytestmark = pytest.mark.gpu
 
@@ -319,7 +320,7 @@ def test_kernel_variants_bitwise(gpu, tune):
 
 @pytest.mark.parametrize("flags", [0, N.TUNE_NO_LDS_BVH, N.TUNE_NO_PRIM_LDS, N.TUNE_NO_RAY_LDS])
 @pytest.mark.parametrize("which", ["cornell", "glass", "pbr"])
-def test_small_scene_lds_bvh_bitwise(gpu, which, flags):
+def test_small_scene_lds_bvh_bitwise(gpu, capfd, which, flags):
     """A scene whose whole BVH4 (inner nodes, leaf records, primitives) fits in 4 KB is
     traversed from every block's LDS copy (C1, C2, C4, C5), its rays kept in LDS too (with
     IZPI_TUNE_NO_RAY_LDS re-read from global memory by the primitive tests); with
@@ -330,11 +331,19 @@ def test_small_scene_lds_bvh_bitwise(gpu, which, flags):
     scene, sampler = {"cornell": (configs.cornell_rgb(), N.SAMPLER_COLOUR),
                       "glass": (configs.cornell_glass_spectral(), N.SAMPLER_SPECTRAL),
                       "pbr": (configs.cornell_pbr(1.0, res=64), N.SAMPLER_COLOUR)}[which]
-    r = GPURenderer(scene, 48, 48, 4, sampler=sampler, tuning=N.tuning(flags=flags) if flags else None)
+    r = GPURenderer(scene, 48, 48, 4, sampler=sampler, tuning=N.tuning(flags=flags | N.TUNE_PASS_LOG))
+    capfd.readouterr()
     img = r.render()
+    err = capfd.readouterr().err
     ref, ostats = oracle_canvas(scene, 48, 48, 4, sampler)
     assert_parity(img, ref, r.stats, ostats)
     r.close()
+    # the instances the flag asks for are the ones that ran: without the tree in LDS only the
+    # triangle-only instance that reads no (u, v) keeps its rays there (the plain box)
+    trace, tables = log_line(err, "IZPI_TRACE_INSTANCE"), log_line(err, "IZPI_SHADE_TABLES")
+    assert trace["lds_bvh"] == int(flags != N.TUNE_NO_LDS_BVH), trace
+    assert trace["ray_lds"] == (0 if flags == N.TUNE_NO_RAY_LDS else int(which == "cornell") if flags == N.TUNE_NO_LDS_BVH else 1), trace
+    assert tables["prims"] == int(flags != N.TUNE_NO_PRIM_LDS), tables
 
 
 @pytest.mark.parametrize("tune", [{"rec_dense": 1, "pool_div": 100000},

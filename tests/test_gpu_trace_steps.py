@@ -19,6 +19,7 @@ from izpi_amd import configs
 from izpi_amd.renderer import GPURenderer
 from izpi_amd.scene import HostScene
 from oracle import oracle as O
+from tests.table_cases import log_line
 from tests.test_gpu_parity import assert_parity
 
 pytestmark = pytest.mark.gpu
@@ -195,11 +196,15 @@ def test_slab_forms_mixed_in_one_wave_bitwise(gpu):
 
 @pytest.mark.parametrize("flags", [0, N.TUNE_NO_RAY_LDS], ids=["ray_lds", "no_ray_lds"])
 @pytest.mark.parametrize("which", ["cornell", "pbr"])
-def test_lds_tree_instances_bitwise(gpu, which, flags):
-    """The instances that traverse the tree from LDS, with the rays in LDS and without."""
+def test_lds_tree_instances_bitwise(gpu, capfd, which, flags):
+    """The instances that traverse the tree from LDS, with the rays in LDS and without: the
+    pass log names the instance that ran."""
     W, H, spp = 48, 48, 4
-    r = GPURenderer(scene_of(which), W, H, spp, tuning=N.tuning(flags=flags) if flags else None)
+    r = GPURenderer(scene_of(which), W, H, spp, tuning=N.tuning(flags=flags | N.TUNE_PASS_LOG))
+    capfd.readouterr()
     img = r.render()
+    trace = log_line(capfd.readouterr().err, "IZPI_TRACE_INSTANCE")
     ref, ostats = oracle_ref(which, W, H, spp)
     assert_parity(img, ref, r.stats, ostats)
     r.close()
+    assert (trace["lds_bvh"], trace["ray_lds"]) == (1, int(flags == 0)), trace
