@@ -357,6 +357,56 @@ int izpi_gpu_render_rank(izpi_ctx* ctx, const izpi_render_req* req, double* out_
 int izpi_gpu_progress(izpi_ctx* ctx, uint64_t* samples_done, uint64_t* samples_total);
 int izpi_gpu_multi_progress(izpi_multi* m, uint64_t* samples_done, uint64_t* samples_total);
 
+/* ---- Progressive rendering ---------------------------------------------------------
+ * render.New's previewChan and a cancellable ctx (render/rgb.go:18-52, spectral.go:20-52),
+ * in the form a wavefront renderer has them: the frame's samples are rendered in steps, the
+ * per-pixel sums stay on the device, and a snapshot normalised by the samples done so far
+ * can be taken after any step. Sample s of a pixel draws from its own stream whatever the
+ * request's spp, and the sums are folded in sample order, so a session that has rendered k
+ * samples in ANY split of steps snapshots exactly the canvas izpi_gpu_render writes at
+ * spp = k, bit for bit, with the same counters.
+ *
+ *  begin     req->spp is the session's cap N; every other field means what it means to
+ *            izpi_gpu_render and is checked as there. The workspace is sized and allocated
+ *            as a request of step_spp samples (>= 1, clipped to N) would size it; the sums
+ *            and counters start at zero. `req` and what it points to are copied. A context
+ *            holds one session: a second begin is IZPI_ERR_INVALID.
+ *  step      renders samples [done, done + min(spp, N - done)); spp == 0 means step_spp. A
+ *            step of more than step_spp samples runs in pieces of at most step_spp. At
+ *            done == N a no-op. stats (may be NULL) are cumulative since begin: the counters
+ *            equal a one-shot render's at spp = done; times and launches are the steps' sums.
+ *  snapshot  resolves the sums, without changing them, into a caller-owned buffer of
+ *            izpi_gpu_output_bytes(req): host memory (read first, as izpi_gpu_render reads
+ *            it: pixels outside the tiles keep their values) or, _device, device memory.
+ *            IZPI_SNAP_CANVAS is what izpi_gpu_render writes at spp = done, req->post
+ *            included. IZPI_SNAP_DISPLAY holds the pixels of display.DisplayTile
+ *            (render/rgb.go:43-51, spectral.go:38-46): B, G, R, 1.0, for the Spectral
+ *            sampler XYZToACEScg of the exposed X, Y, Z (rgb_image.go:13-22), without
+ *            FireflyRejection and without req->post; same layout. IZPI_ERR_INVALID before
+ *            the first sample.
+ *  end       closes the session (the cancellation point: a caller whose ctx is cancelled
+ *            stops stepping and ends). The workspace stays with the context.
+ * While a session is open izpi_gpu_render, _render_device, _render_rank, _prepare,
+ * _upload_scene, _trace and _debug_realloc return IZPI_ERR_INVALID and leave it intact;
+ * izpi_gpu_close ends it; izpi_gpu_progress reports (pixels * done + the running step's
+ * progress, pixels * N). */
+enum { IZPI_SNAP_CANVAS = 0, IZPI_SNAP_DISPLAY = 1 };
+int izpi_gpu_progressive_begin(izpi_ctx* ctx, const izpi_render_req* req, uint32_t step_spp);
+int izpi_gpu_progressive_step(izpi_ctx* ctx, uint32_t spp, izpi_render_stats* stats);
+int izpi_gpu_progressive_snapshot(izpi_ctx* ctx, uint32_t form, double* out_host);
+int izpi_gpu_progressive_snapshot_device(izpi_ctx* ctx, uint32_t form, double* out_dev);
+int izpi_gpu_progressive_end(izpi_ctx* ctx);
+/* The same over the devices of `m`, with izpi_gpu_multi_render's share plan: every device
+ * holds a session over its share's units (packed), steps run on the per-device threads, and a
+ * snapshot gathers the resolved shares to device 0, which scatters them into the canvas and
+ * applies req->post (IZPI_SNAP_CANVAS). out_host: the caller's W*H*4 canvas, read first.
+ * stats: [num_devices] or NULL. izpi_gpu_multi_render, _multi_prepare and _multi_upload_scene
+ * return IZPI_ERR_INVALID while the session is open. */
+int izpi_gpu_multi_progressive_begin(izpi_multi* m, const izpi_render_req* req, uint32_t step_spp);
+int izpi_gpu_multi_progressive_step(izpi_multi* m, uint32_t spp, izpi_render_stats* stats);
+int izpi_gpu_multi_progressive_snapshot(izpi_multi* m, uint32_t form, double* out_host);
+int izpi_gpu_multi_progressive_end(izpi_multi* m);
+
 /* Bytes of device output izpi_gpu_render_device writes for `req`. */
 uint64_t izpi_gpu_output_bytes(const izpi_render_req* req);
 

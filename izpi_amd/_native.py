@@ -27,6 +27,7 @@ MATF_BEER_LAMBERT = 1
 SAMPLER_NORMAL, SAMPLER_COLOUR, SAMPLER_WIREFRAME, SAMPLER_ALBEDO, SAMPLER_SPECTRAL = 1, 2, 3, 4, 5  # sampler.go:13-20
 OUT_CANVAS, OUT_PACKED = 0, 1
 POST_NONE, POST_SPECTRAL, POST_GAMMA_CLAMP = 0, 1, 2
+SNAP_CANVAS, SNAP_DISPLAY = 0, 1  # izpi_gpu_progressive_snapshot's forms
 FILTER_GAMMA, FILTER_CLAMP = 1, 2
 MAX_FILTERS = 8
 HOST_SKIP_BVH = 1
@@ -219,6 +220,10 @@ EXPORTS = [
     "izpi_obj_group_to_triangles", "izpi_obj_free",
     "izpi_gpu_displace", "izpi_host_displace", "izpi_scene_displacement_file", "izpi_scene_set_displacement_map",
     "izpi_scene_set_displacer",
+    "izpi_gpu_progressive_begin", "izpi_gpu_progressive_step", "izpi_gpu_progressive_snapshot",
+    "izpi_gpu_progressive_snapshot_device", "izpi_gpu_progressive_end",
+    "izpi_gpu_multi_progressive_begin", "izpi_gpu_multi_progressive_step", "izpi_gpu_multi_progressive_snapshot",
+    "izpi_gpu_multi_progressive_end",
 ]
 
 _lib = None
@@ -273,6 +278,12 @@ def lib():
     L.izpi_gpu_debug_realloc.argtypes = [C.c_void_p, C.c_uint32]
     L.izpi_gpu_progress.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.izpi_gpu_multi_progress.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    for pre in ("izpi_gpu_progressive_", "izpi_gpu_multi_progressive_"):
+        getattr(L, pre + "begin").argtypes = [C.c_void_p, C.POINTER(RenderReq), C.c_uint32]
+        getattr(L, pre + "step").argtypes = [C.c_void_p, C.c_uint32, C.POINTER(RenderStats)]
+        getattr(L, pre + "snapshot").argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        getattr(L, pre + "end").argtypes = [C.c_void_p]
+    L.izpi_gpu_progressive_snapshot_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
     L.izpi_host_build_scene_ex.argtypes = [C.POINTER(SceneInput), C.c_uint32, C.POINTER(C.c_void_p)]
     L.izpi_host_scene_prim_boxes.argtypes = [C.c_void_p, c_double_p]
     L.izpi_host_scene_set_bvh.argtypes = [C.c_void_p, C.POINTER(BVH4Node), C.c_uint32, c_uint32_p]

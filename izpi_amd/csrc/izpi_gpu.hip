@@ -381,6 +381,14 @@ int apply_post(izpi_ctx* ctx, const izpi_render_req* req, double* canvas_dev) {
   return IZPI_OK;
 }
 
+// A step of a progressive session finds the workspace its begin allocated: were a buffer to
+// be re-allocated (`moved`), the running sums would go with it.
+int session_keeps_sums(izpi_ctx* ctx, const SampleRange& sr, bool moved) {
+  if (!sr.keep || ctx->prepare_only || !moved) return IZPI_OK;
+  ctx->err = "progressive step: the session's workspace no longer fits (its sums would be lost)";
+  return IZPI_ERR_INVALID;
+}
+
 // The preview samplers' entries, `slots` of them, in izpi_ctx::d_state: returns the bytes
 // (base == nullptr) or fills pp.buf and pp.tminmax.
 size_t carve_preview(char* base, uint32_t slots, bool time, bool uv, bool wire, PreviewParams* pp) {
@@ -408,10 +416,11 @@ size_t carve_preview(char* base, uint32_t slots, bool time, bool uv, bool wire, 
 // rays, hits and per-sample results only (no records, pool, or second side of the state),
 // within the buffers a Colour render of this context may already hold (they only grow here).
 int preview_body(izpi_ctx* ctx, const izpi_render_req* req, const DevScene& sc, const Tracer& tr, const izpi_render_tuning& tu,
-                 const std::vector<uint32_t>& tiles, uint32_t tw, uint32_t th, uint32_t num_pixels, double* out_dev) {
+                 const std::vector<uint32_t>& tiles, uint32_t tw, uint32_t th, uint32_t num_pixels, const SampleRange& sr,
+                 uint32_t size_spp, double* out_dev) {
   const bool wire = req->sampler == IZPI_SAMPLER_WIREFRAME;
   const bool need_time = !ctx->sc.tri_only, need_uv = !ctx->sc.tri_only || ctx->any_uv;
-  const uint64_t size_key[8] = {num_pixels, req->spp, req->sampler, tu.slots, tu.chunk_units, 0, 0, 0};
+  const uint64_t size_key[8] = {num_pixels, size_spp, req->sampler, tu.slots, tu.chunk_units, 0, 0, 0};
   const bool reuse = ctx->pv_sizing_valid && memcmp(size_key, ctx->pv_sizing.key, sizeof(size_key)) == 0;
   uint32_t chunk = ctx->pv_sizing.chunk, slots = ctx->pv_sizing.slots;
   if (!reuse) {
@@ -422,9 +431,9 @@ int preview_body(izpi_ctx* ctx, const izpi_render_req* req, const DevScene& sc, 
     const uint64_t avail = free_b ? ((uint64_t)free_b + render_buffer_bytes(ctx)) / std::max(1u, ctx->dev_share) : 0;
     uint64_t max_units = std::max<uint64_t>(64ull << 20, (avail / 8) / (SMP_D * sizeof(double)));
     if (tu.chunk_units) max_units = tu.chunk_units;
-    chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(req->spp, max_units / num_pixels));
-    const uint32_t nchunks = (req->spp + chunk - 1) / chunk;
-    chunk = (req->spp + nchunks - 1) / nchunks;
+    chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(size_spp, max_units / num_pixels));
+    const uint32_t nchunks = (size_spp + chunk - 1) / chunk;
+    chunk = (size_spp + nchunks - 1) / nchunks;
     uint64_t slot_cap = 256ull << 20;
     if (tu.slots) slot_cap = std::max<uint64_t>(1024, tu.slots);
     const uint64_t per_slot = carve_preview(nullptr, 1024, need_time, need_uv, wire, nullptr) / 1024 + 1;
@@ -440,6 +449,7 @@ int preview_body(izpi_ctx* ctx, const izpi_render_req* req, const DevScene& sc, 
   const size_t state_bytes = carve_preview(nullptr, slots, need_time, need_uv, wire, nullptr);
   const uint32_t cpart_rows = ctx->num_cus * CPART_BLOCKS_PER_CU * 4u;
   int rc;
+  if ((rc = session_keeps_sums(ctx, sr, ctx->running_cap < (size_t)num_pixels * 3 * sizeof(double)))) return rc;
   if ((rc = grow(ctx, (void**)&ctx->d_samples, &ctx->samples_cap, samples_bytes)) ||
       (rc = grow(ctx, (void**)&ctx->d_running, &ctx->running_cap, (size_t)num_pixels * 3 * sizeof(double))) ||
       (rc = grow(ctx, (void**)&ctx->d_state, &ctx->state_cap, state_bytes)) ||
@@ -454,6 +464,10 @@ int preview_body(izpi_ctx* ctx, const izpi_render_req* req, const DevScene& sc, 
   if (ctx->prepare_only) {  // izpi_gpu_prepare: the device's first work on the workspace, as render_body
     HIP_TRY(hipMemsetAsync(ctx->d_state, 0, state_bytes, st));
     HIP_TRY(hipMemsetAsync(ctx->d_samples, 0, samples_bytes, st));
+    if (sr.keep) {  // izpi_gpu_progressive_begin: the session's sums and counters start at zero
+      HIP_TRY(hipMemsetAsync(ctx->d_running, 0, (size_t)num_pixels * 3 * sizeof(double), st));
+      HIP_TRY(hipMemsetAsync(ctx->d_counters, 0, CNT_N * sizeof(unsigned long long), st));
+    }
     HIP_TRY(hipStreamSynchronize(st));
     ctx->last = izpi_render_stats{};
     ctx->last.workspace_bytes = workspace_bytes(ctx);
@@ -461,8 +475,10 @@ int preview_body(izpi_ctx* ctx, const izpi_render_req* req, const DevScene& sc, 
     return IZPI_OK;
   }
   HIP_TRY(hipMemcpyAsync(ctx->d_tiles, tiles.data(), tiles.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemsetAsync(ctx->d_running, 0, (size_t)num_pixels * 3 * sizeof(double), st));
-  HIP_TRY(hipMemsetAsync(ctx->d_counters, 0, CNT_N * sizeof(unsigned long long), st));
+  if (!sr.keep) {  // (a session's sums and counters run on from step to step)
+    HIP_TRY(hipMemsetAsync(ctx->d_running, 0, (size_t)num_pixels * 3 * sizeof(double), st));
+    HIP_TRY(hipMemsetAsync(ctx->d_counters, 0, CNT_N * sizeof(unsigned long long), st));
+  }
   HIP_TRY(hipMemsetAsync(ctx->d_cpart, 0, (size_t)cpart_rows * CNT_N * sizeof(unsigned long long), st));
   HIP_TRY(hipMemsetAsync(ctx->d_misc, 0, 8 * MISC_STRIDE * sizeof(uint32_t), st));
   ShadeParams sp{};
@@ -484,11 +500,11 @@ int preview_body(izpi_ctx* ctx, const izpi_render_req* req, const DevScene& sc, 
   float trace_ms = 0, shade_ms = 0, total_ms = 0;
   uint32_t launches = 0;
   HIP_TRY(hipEventRecord(ctx->ev0, st));
-  if ((rc = run_preview(ctx, req, sc, tr, sp, pp, ap, num_pixels, chunk, &trace_ms, &shade_ms, &launches))) return rc;
+  if ((rc = run_preview(ctx, req, sc, tr, sp, pp, ap, num_pixels, chunk, sr, &trace_ms, &shade_ms, &launches))) return rc;
   hipLaunchKernelGGL(k_cpart_reduce, dim3(CNT_N), dim3(256), 0, st, ctx->d_cpart, cpart_rows, ctx->d_counters);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(ctx->ev1, st));
-  if ((rc = apply_post(ctx, req, out_dev))) return rc;
+  if (!sr.keep && (rc = apply_post(ctx, req, out_dev))) return rc;
   HIP_TRY(hipEventSynchronize(ctx->ev1));
   HIP_TRY(hipEventElapsedTime(&total_ms, ctx->ev0, ctx->ev1));
   unsigned long long cnt[CNT_N];
@@ -498,7 +514,7 @@ int preview_body(izpi_ctx* ctx, const izpi_render_req* req, const DevScene& sc, 
   izpi_render_stats& s = ctx->last;
   memset(&s, 0, sizeof(s));
   s.rays = cnt[CNT_RAYS]; s.node_visits = cnt[CNT_NODES]; s.tri_tests = cnt[CNT_TRI]; s.sph_tests = cnt[CNT_SPH];
-  s.samples = (uint64_t)num_pixels * req->spp;
+  s.samples = (uint64_t)num_pixels * sr.end;
   s.kernel_ms = trace_ms; s.shade_ms = shade_ms; s.total_ms = total_ms; s.launches = launches;
   s.node_steps = cnt[CNT_NSTEP]; s.prim_steps = cnt[CNT_PSTEP]; s.leaf_shortcuts = cnt[CNT_SHORT];
   s.workspace_bytes = workspace_bytes(ctx);
@@ -508,10 +524,19 @@ int preview_body(izpi_ctx* ctx, const izpi_render_req* req, const DevScene& sc, 
   return IZPI_OK;
 }
 
+// A progressive session owns the context's running sums, counters and progress: the calls
+// that would overwrite them are refused while it is open.
+bool session_open(izpi_ctx* ctx) {
+  if (!ctx->session.open) return false;
+  ctx->err = "a progressive session is open";
+  return true;
+}
+
 int render_body(izpi_ctx* ctx, const izpi_render_req* req, double* out_dev);
 // One render on one context. The progress counters (izpi_gpu_progress) start at 0/0 before
 // any check and read done == total on every return, failed calls included.
 int render_impl(izpi_ctx* ctx, const izpi_render_req* req, double* out_dev) {
+  if (session_open(ctx)) return IZPI_ERR_INVALID;  // (before the progress counters: they are the session's)
   ctx->prog_done.store(0, std::memory_order_relaxed);
   ctx->prog_total.store(0, std::memory_order_relaxed);
   const int rc = render_body(ctx, req, out_dev);
@@ -561,6 +586,14 @@ int render_body(izpi_ctx* ctx, const izpi_render_req* req, double* out_dev) {
   if (num_pixels64 > (1ull << 30)) { ctx->err = "too many pixels in one request"; return IZPI_ERR_INVALID; }
   const uint32_t num_pixels = (uint32_t)num_pixels64;
   ctx->prog_total.store(num_pixels64 * req->spp, std::memory_order_relaxed);
+  // The samples this call renders and the samples its workspace is sized for: the request's,
+  // or a progressive session's step and its step_spp (the sums then stay in d_running).
+  const SampleRange sr = ctx->range ? *ctx->range : SampleRange{0, req->spp, false};
+  const uint32_t size_spp = ctx->range ? ctx->size_spp : req->spp;
+  if (sr.keep) {
+    izpi_ctx::Session& ss = ctx->session;
+    ss.run_tiles = tiles; ss.tile_w = tw; ss.tile_h = th; ss.num_pixels = num_pixels;
+  }
   if (ctx->stack_needed > 64) { ctx->err = "BVH deeper than the 64-entry traversal stack (bvh4.go:71)"; return IZPI_ERR_UNSUPPORTED; }
   const izpi_render_tuning& tu = tuning_of(req);
   // this render's view of the scene: the traversal shortcuts the tuning switches off
@@ -575,11 +608,11 @@ int render_body(izpi_ctx* ctx, const izpi_render_req* req, double* out_dev) {
     fprintf(stderr, "IZPI_TRACE_INSTANCE dist=%d tri=%d lds_bvh=%d ray_lds=%d q=%d\n", (int)tr.p2, (int)tr.tri, (int)tr.lds_bvh,
             (int)tr.ray_lds, (int)tr.qnodes);
   const double t_tracer = host_ms();
-  if (preview) return preview_body(ctx, req, sc, tr, tu, tiles, tw, th, num_pixels, out_dev);
+  if (preview) return preview_body(ctx, req, sc, tr, tu, tiles, tw, th, num_pixels, sr, size_spp, out_dev);
   // Sizing against the HBM this context may use: what is free plus the render buffers it
   // holds and would release (a later frame reuses them, so every frame of a renderer sizes
   // alike), shared evenly by the contexts of one process on this device.
-  const uint64_t size_key[8] = {num_pixels, req->spp, req->sampler, req->max_depth, ctx->pool_grow,
+  const uint64_t size_key[8] = {num_pixels, size_spp, req->sampler, req->max_depth, ctx->pool_grow,
                                 ((uint64_t)tu.slots << 32) | tu.chunk_units, ((uint64_t)tu.rec_dense << 32) | tu.pool_div, acc};
   const bool reuse = ctx->sizing_valid && memcmp(size_key, ctx->sizing.key, sizeof(size_key)) == 0;
   size_t free_b = 0, total_b = 0;
@@ -599,9 +632,9 @@ int render_body(izpi_ctx* ctx, const izpi_render_req* req, double* out_dev) {
   if (tu.chunk_units) max_units = tu.chunk_units;
   // the chunks of a request are balanced: as many as the limit needs, equal in size (C4 at
   // 1024 spp: 2 chunks of 512 instead of 774 + 250, 13 GB less to allocate, same drains)
-  uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(req->spp, max_units / num_pixels));
-  const uint32_t nchunks = (req->spp + chunk - 1) / chunk;
-  chunk = (req->spp + nchunks - 1) / nchunks;
+  uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(size_spp, max_units / num_pixels));
+  const uint32_t nchunks = (size_spp + chunk - 1) / chunk;
+  chunk = (size_spp + nchunks - 1) / nchunks;
   if (reuse) chunk = ctx->sizing.chunk;
   // Unwinding records: the first rec_dense levels per slot, deeper levels in overflow
   // blocks (ShadeParams::rec_pool). Colour records are 40 B (24 B compact), spectral 24 B.
@@ -691,6 +724,7 @@ int render_body(izpi_ctx* ctx, const izpi_render_req* req, double* out_dev) {
     ctx->sizing_valid = false;
     return rc;
   }
+  if ((rc = session_keeps_sums(ctx, sr, fresh))) return rc;
   if ((rc = grow(ctx, (void**)&ctx->d_tiles, &ctx->tiles_cap, tiles.size() * sizeof(uint32_t)))) return rc;
   const size_t nbg = req->num_bg_spd;
   if (nbg && (!req->bg_spd_wavelengths || !req->bg_spd_values)) { ctx->err = "num_bg_spd without the SPD arrays"; return IZPI_ERR_INVALID; }
@@ -709,6 +743,10 @@ int render_body(izpi_ctx* ctx, const izpi_render_req* req, double* out_dev) {
     HIP_TRY(hipMemsetAsync(ctx->d_state, 0, ctx->state_cap, ps));
     HIP_TRY(hipMemsetAsync(ctx->d_samples, 0, ctx->samples_cap, ps));
     if (ctx->d_recs) HIP_TRY(hipMemsetAsync(ctx->d_recs, 0, ctx->recs_cap, ps));
+    if (sr.keep) {  // izpi_gpu_progressive_begin: the session's sums and counters start at zero
+      HIP_TRY(hipMemsetAsync(ctx->d_running, 0, (size_t)num_pixels * 3 * sizeof(double), ps));
+      HIP_TRY(hipMemsetAsync(ctx->d_counters, 0, CNT_N * sizeof(unsigned long long), ps));
+    }
     HIP_TRY(hipStreamSynchronize(ps));
     ctx->last = izpi_render_stats{};
     ctx->last.workspace_bytes = workspace_bytes(ctx);
@@ -724,8 +762,10 @@ int render_body(izpi_ctx* ctx, const izpi_render_req* req, double* out_dev) {
     HIP_TRY(hipMemcpyAsync(ctx->d_bg, req->bg_spd_wavelengths, nbg * sizeof(double), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(ctx->d_bg + nbg, req->bg_spd_values, nbg * sizeof(double), hipMemcpyHostToDevice, st));
   }
-  HIP_TRY(hipMemsetAsync(ctx->d_running, 0, (size_t)num_pixels * 3 * sizeof(double), st));
-  HIP_TRY(hipMemsetAsync(ctx->d_counters, 0, CNT_N * sizeof(unsigned long long), st));
+  if (!sr.keep) {  // (a session's sums and counters run on from step to step)
+    HIP_TRY(hipMemsetAsync(ctx->d_running, 0, (size_t)num_pixels * 3 * sizeof(double), st));
+    HIP_TRY(hipMemsetAsync(ctx->d_counters, 0, CNT_N * sizeof(unsigned long long), st));
+  }
   HIP_TRY(hipMemsetAsync(ctx->d_cpart, 0, (size_t)cpart_rows * CNT_N * sizeof(unsigned long long), st));
   HIP_TRY(hipMemsetAsync(ctx->d_misc, 0, 8 * MISC_STRIDE * sizeof(uint32_t), st));
 
@@ -785,8 +825,8 @@ int render_body(izpi_ctx* ctx, const izpi_render_req* req, double* out_dev) {
     fprintf(stderr, "IZPI_T ev0_synced %.3f prep_gpu_ms %.3f body_start %.3f\n", diag_clock_ms(), prep,
             diag_clock_ms() - host_ms());
   }
-#define IZPI_RUN(S, F) run_sampler<S, F>(ctx, req, sc, tr, sp, wp, ap, num_pixels, chunk, pool_blocks, compact, &trace_ms, &shade_ms, \
-                                        &tail_ms, &launches)
+#define IZPI_RUN(S, F) run_sampler<S, F>(ctx, req, sc, tr, sp, wp, ap, num_pixels, chunk, pool_blocks, compact, sr, &trace_ms, \
+                                        &shade_ms, &tail_ms, &launches)
   if (req->sampler == IZPI_SAMPLER_COLOUR) rc = fwd ? IZPI_RUN(IZPI_SAMPLER_COLOUR, true) : IZPI_RUN(IZPI_SAMPLER_COLOUR, false);
   else rc = fwd ? IZPI_RUN(IZPI_SAMPLER_SPECTRAL, true) : IZPI_RUN(IZPI_SAMPLER_SPECTRAL, false);
 #undef IZPI_RUN
@@ -794,7 +834,7 @@ int render_body(izpi_ctx* ctx, const izpi_render_req* req, double* out_dev) {
   hipLaunchKernelGGL(k_cpart_reduce, dim3(CNT_N), dim3(256), 0, st, ctx->d_cpart, cpart_rows, ctx->d_counters);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(ctx->ev1, st));
-  if ((rc = apply_post(ctx, req, out_dev))) return rc;
+  if (!sr.keep && (rc = apply_post(ctx, req, out_dev))) return rc;
   const double t_issued = host_ms();
   HIP_TRY(hipEventSynchronize(ctx->ev1));
   if (tu.flags & IZPI_TUNE_PASS_LOG)  // diagnostics: where the call's host time goes
@@ -810,7 +850,7 @@ int render_body(izpi_ctx* ctx, const izpi_render_req* req, double* out_dev) {
   memset(&s, 0, sizeof(s));
   s.rays = cnt[CNT_RAYS]; s.node_visits = cnt[CNT_NODES]; s.tri_tests = cnt[CNT_TRI]; s.sph_tests = cnt[CNT_SPH];
   s.light_tri_tests = cnt[CNT_LTRI]; s.light_sph_tests = cnt[CNT_LSPH];
-  s.samples = (uint64_t)num_pixels * req->spp;
+  s.samples = (uint64_t)num_pixels * sr.end;
   s.kernel_ms = trace_ms; s.shade_ms = shade_ms; s.total_ms = total_ms; s.launches = launches; s.tail_ms = tail_ms;
   s.node_steps = cnt[CNT_NSTEP]; s.prim_steps = cnt[CNT_PSTEP]; s.leaf_shortcuts = cnt[CNT_SHORT];
   s.tail_node_visits = cnt[CNT_TAIL_NODES]; s.tail_tri_tests = cnt[CNT_TAIL_TRI]; s.tail_sph_tests = cnt[CNT_TAIL_SPH];
@@ -819,7 +859,8 @@ int render_body(izpi_ctx* ctx, const izpi_render_req* req, double* out_dev) {
   s.scene_bytes = ctx->scene_bytes;
   s.slots = slots; s.rec_dense = fwd ? 0 : rec_dense; s.pool_blocks = pool_blocks; s.chunk_spp = chunk;
   s.alloc_ms = alloc_ms;
-  if (rec_pool && s.parks * 64 > s.rays && pool_blocks < slots) ctx->pool_grow++;
+  // (not within a session: a larger pool would re-allocate the workspace, the sums with it)
+  if (!sr.keep && rec_pool && s.parks * 64 > s.rays && pool_blocks < slots) ctx->pool_grow++;
 #ifdef IZPI_SHADE_CLOCKS
   fprintf(stderr, "IZPI_SHADE_CLOCKS item %llu refill %llu push %llu mat %llu finish %llu mix %llu lpdf %llu entry %llu tex %llu "
           "res_barrier1 %llu res_atomics %llu res_barrier2 %llu (wave cycles; res_atomics: thread 0 only)\n",
@@ -932,12 +973,130 @@ int assemble(izpi_ctx* ctx, const izpi_render_req* req, const Shares& sh, double
   return IZPI_OK;
 }
 
+// ------------------------------------------------------- progressive sessions
+// The library's own copy of a session's request and of the arrays it points to.
+int session_copy_request(izpi_ctx::Session& ss, const izpi_render_req* req, std::string& err) {
+  ss = izpi_ctx::Session{};
+  ss.req = request_copy(req);
+  ss.tuning = tuning_of(req);
+  ss.req.tuning = req->tuning ? &ss.tuning : nullptr;
+  if (ss.req.num_tiles) {
+    if (!ss.req.tiles) { err = "num_tiles without tiles"; return IZPI_ERR_INVALID; }
+    ss.tiles.assign(ss.req.tiles, ss.req.tiles + 4 * (size_t)ss.req.num_tiles);
+    ss.req.tiles = ss.tiles.data();
+  }
+  if (ss.req.num_bg_spd) {
+    if (!ss.req.bg_spd_wavelengths || !ss.req.bg_spd_values) { err = "num_bg_spd without the SPD arrays"; return IZPI_ERR_INVALID; }
+    ss.bg_wl.assign(ss.req.bg_spd_wavelengths, ss.req.bg_spd_wavelengths + ss.req.num_bg_spd);
+    ss.bg_val.assign(ss.req.bg_spd_values, ss.req.bg_spd_values + ss.req.num_bg_spd);
+    ss.req.bg_spd_wavelengths = ss.bg_wl.data();
+    ss.req.bg_spd_values = ss.bg_val.data();
+  }
+  return IZPI_OK;
+}
+
+void session_drop(izpi_ctx* ctx) {
+  ctx->session = izpi_ctx::Session{};
+  ctx->prog_done.store(0, std::memory_order_relaxed);
+  ctx->prog_total.store(0, std::memory_order_relaxed);
+}
+
+// begin: render_body's own checks, sizing and allocation for a request of step_spp samples
+// (its prepare_only form, which for a session also zeroes the sums and the counters).
+int session_begin(izpi_ctx* ctx, const izpi_render_req* req, uint32_t step_spp) {
+  if (ctx->session.open) { ctx->err = "a progressive session is already open"; return IZPI_ERR_INVALID; }
+  if (!req || step_spp == 0) { ctx->err = "progressive_begin: a request and step_spp >= 1"; return IZPI_ERR_INVALID; }
+  izpi_ctx::Session& ss = ctx->session;
+  int rc = session_copy_request(ss, req, ctx->err);
+  if (!rc) {
+    ss.step_spp = std::min(step_spp, std::max(1u, ss.req.spp));
+    const SampleRange sr{0, 0, true};
+    ctx->range = &sr; ctx->size_spp = ss.step_spp; ctx->prepare_only = true;
+    rc = render_body(ctx, &ss.req, nullptr);
+    ctx->range = nullptr; ctx->prepare_only = false;
+  }
+  if (rc) {
+    const std::string why = ctx->err;
+    session_drop(ctx);
+    ctx->err = why;
+    return rc;
+  }
+  ss.cum = izpi_render_stats{};
+  ss.open = true;
+  ctx->prog_done.store(0, std::memory_order_relaxed);
+  ctx->prog_total.store((uint64_t)ss.num_pixels * ss.req.spp, std::memory_order_relaxed);
+  return IZPI_OK;
+}
+
+int session_usable(izpi_ctx* ctx) {
+  if (!ctx->session.open) { ctx->err = "no progressive session is open"; return IZPI_ERR_INVALID; }
+  if (ctx->session.broken) { ctx->err = "the session's last step failed: end it"; return IZPI_ERR_INVALID; }
+  return IZPI_OK;
+}
+
+// step: samples [done, done + n) through render_body's chunk loops, never finalised. The
+// device counters run on from step to step; times and launches are summed here.
+int session_step(izpi_ctx* ctx, uint32_t spp, izpi_render_stats* stats) {
+  int rc = session_usable(ctx);
+  if (rc) return rc;
+  izpi_ctx::Session& ss = ctx->session;
+  const uint32_t n = std::min(spp ? spp : ss.step_spp, ss.req.spp - ss.done);
+  if (n) {
+    const SampleRange sr{ss.done, ss.done + n, true};
+    ctx->range = &sr; ctx->size_spp = ss.step_spp;
+    rc = render_body(ctx, &ss.req, nullptr);
+    ctx->range = nullptr;
+    if (rc) {  // a chunk may or may not be in the sums
+      ss.broken = true;
+      return rc;
+    }
+    ss.done += n;
+    izpi_render_stats s = ctx->last;
+    s.kernel_ms += ss.cum.kernel_ms; s.shade_ms += ss.cum.shade_ms; s.tail_ms += ss.cum.tail_ms;
+    s.total_ms += ss.cum.total_ms; s.alloc_ms += ss.cum.alloc_ms; s.launches += ss.cum.launches;
+    ss.cum = s;
+    ctx->last = s;
+    ctx->prog_done.store((uint64_t)ss.num_pixels * ss.done, std::memory_order_relaxed);
+  }
+  if (stats) *stats = ss.cum;
+  return IZPI_OK;
+}
+
+// snapshot: k_resolve of the sums into device memory, then (IZPI_SNAP_CANVAS) the request's post.
+int session_snapshot(izpi_ctx* ctx, uint32_t form, double* out_dev) {
+  int rc = session_usable(ctx);
+  if (rc) return rc;
+  const izpi_ctx::Session& ss = ctx->session;
+  if (form != IZPI_SNAP_CANVAS && form != IZPI_SNAP_DISPLAY) { ctx->err = "unknown snapshot form"; return IZPI_ERR_INVALID; }
+  if (ss.done == 0) { ctx->err = "snapshot before the session's first sample"; return IZPI_ERR_INVALID; }
+  if (!out_dev) { ctx->err = "null output"; return IZPI_ERR_INVALID; }
+  hipStream_t st = ctx->stream;
+  // (izpi_gpu_unpack_tiles may have used d_tiles since the last step)
+  if ((rc = grow(ctx, (void**)&ctx->d_tiles, &ctx->tiles_cap, ss.run_tiles.size() * sizeof(uint32_t)))) return rc;
+  HIP_TRY(hipMemcpyAsync(ctx->d_tiles, ss.run_tiles.data(), ss.run_tiles.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  ResolveParams rp{};
+  rp.num_pixels = ss.num_pixels; rp.done = ss.done; rp.width = ss.req.width; rp.height = ss.req.height;
+  rp.tile_w = ss.tile_w; rp.tile_h = ss.tile_h; rp.sampler = ss.req.sampler; rp.out_layout = ss.req.out_layout;
+  rp.form = form; rp.exposure = ss.req.exposure;
+  rp.tiles = ctx->d_tiles; rp.running = ctx->d_running; rp.out = out_dev;
+  launch_resolve(st, rp);
+  HIP_TRY(hipGetLastError());
+  if (form == IZPI_SNAP_CANVAS && (rc = apply_post(ctx, &ss.req, out_dev))) return rc;
+  HIP_TRY(hipStreamSynchronize(st));
+  return IZPI_OK;
+}
+
 }  // namespace
 
 // One context per device of a single-process multi-GPU render (izpi_gpu_multi_*).
 struct izpi_multi {
   std::vector<izpi_ctx*> ctx;
   std::string err;
+  // the progressive session over the devices (izpi_gpu_multi_progressive_*): the request (and
+  // step_spp, done), and the share plan its devices' sessions were opened with
+  bool prog_open = false;
+  izpi_ctx::Session session;
+  Shares shares;
 };
 
 namespace {
@@ -972,6 +1131,12 @@ int on_every_device(izpi_multi* m, F fn) {
   return IZPI_OK;
 }
 
+bool multi_session_open(izpi_multi* m) {
+  if (!m->prog_open) return false;
+  m->err = "a progressive session is open";
+  return true;
+}
+
 static_assert(sizeof(Double4) == sizeof(double4), "PackedScene::mat_const uploads as DevScene::mat_const");
 
 // izpi_gpu_upload_scene's first steps: the context is idle on its device and holds no scene.
@@ -979,6 +1144,7 @@ int begin_upload(izpi_ctx* ctx, const izpi_scene_desc* d) {
   if (!ctx || !d) return IZPI_ERR_INVALID;
   // the scene descriptor is laid out alike in ABI 1 and 2
   if (d->abi_version < 1 || d->abi_version > IZPI_ABI_VERSION) { ctx->err = "ABI version mismatch"; return IZPI_ERR_INVALID; }
+  if (session_open(ctx)) return IZPI_ERR_INVALID;
   HIP_TRY(hipSetDevice(ctx->device));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   free_scene(ctx);
@@ -1138,6 +1304,7 @@ int izpi_gpu_render_device(izpi_ctx* ctx, const izpi_render_req* req, double* ou
 int izpi_gpu_render(izpi_ctx* ctx, const izpi_render_req* req, double* out_host, izpi_render_stats* stats) {
   if (!ctx) return IZPI_ERR_INVALID;
   if (!out_host || !req) { ctx->err = "null argument"; return IZPI_ERR_INVALID; }
+  if (session_open(ctx)) return IZPI_ERR_INVALID;
   HIP_TRY(hipSetDevice(ctx->device));
   const size_t bytes = izpi_gpu_output_bytes(req);
   int rc = grow(ctx, (void**)&ctx->d_out, &ctx->out_cap, bytes);
@@ -1155,6 +1322,7 @@ int izpi_gpu_render(izpi_ctx* ctx, const izpi_render_req* req, double* out_host,
 int izpi_gpu_prepare(izpi_ctx* ctx, const izpi_render_req* req) {
   if (!ctx) return IZPI_ERR_INVALID;
   if (!req) { ctx->err = "null argument"; return IZPI_ERR_INVALID; }
+  if (session_open(ctx)) return IZPI_ERR_INVALID;
   HIP_TRY(hipSetDevice(ctx->device));
   if (ctx->comm && ctx->comm_size > 1) {  // izpi_gpu_render_rank's share of the frame on this rank
     Shares sh;
@@ -1166,6 +1334,47 @@ int izpi_gpu_prepare(izpi_ctx* ctx, const izpi_render_req* req) {
   const int rc = render_impl(ctx, req, nullptr);
   ctx->prepare_only = false;
   return rc;
+}
+
+int izpi_gpu_progressive_begin(izpi_ctx* ctx, const izpi_render_req* req, uint32_t step_spp) {
+  if (!ctx) return IZPI_ERR_INVALID;
+  HIP_TRY(hipSetDevice(ctx->device));
+  return session_begin(ctx, req, step_spp);
+}
+
+int izpi_gpu_progressive_step(izpi_ctx* ctx, uint32_t spp, izpi_render_stats* stats) {
+  if (!ctx) return IZPI_ERR_INVALID;
+  HIP_TRY(hipSetDevice(ctx->device));
+  return session_step(ctx, spp, stats);
+}
+
+int izpi_gpu_progressive_snapshot_device(izpi_ctx* ctx, uint32_t form, double* out_dev) {
+  if (!ctx) return IZPI_ERR_INVALID;
+  HIP_TRY(hipSetDevice(ctx->device));
+  return session_snapshot(ctx, form, out_dev);
+}
+
+int izpi_gpu_progressive_snapshot(izpi_ctx* ctx, uint32_t form, double* out_host) {
+  if (!ctx) return IZPI_ERR_INVALID;
+  if (!out_host) { ctx->err = "null output"; return IZPI_ERR_INVALID; }
+  int rc = session_usable(ctx);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(ctx->device));
+  const size_t bytes = izpi_gpu_output_bytes(&ctx->session.req);
+  if ((rc = grow(ctx, (void**)&ctx->d_out, &ctx->out_cap, bytes))) return rc;
+  // start from the caller's buffer so untouched pixels keep their values, as izpi_gpu_render
+  HIP_TRY(hipMemcpyAsync(ctx->d_out, out_host, bytes, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = session_snapshot(ctx, form, ctx->d_out))) return rc;
+  HIP_TRY(hipMemcpyAsync(out_host, ctx->d_out, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return IZPI_OK;
+}
+
+int izpi_gpu_progressive_end(izpi_ctx* ctx) {
+  if (!ctx) return IZPI_ERR_INVALID;
+  if (!ctx->session.open) { ctx->err = "no progressive session is open"; return IZPI_ERR_INVALID; }
+  session_drop(ctx);
+  return IZPI_OK;
 }
 
 int izpi_gpu_spectral_post(izpi_ctx* ctx, const double* xyz_dev, double* rgba_dev, uint32_t width, uint32_t height,
@@ -1274,6 +1483,7 @@ int izpi_gpu_unpack_tiles(izpi_ctx* ctx, const izpi_render_req* req, const doubl
 int izpi_gpu_trace(izpi_ctx* ctx, const double* rays, uint32_t n, izpi_hit* out) {
   if (!ctx || !rays || !out) return IZPI_ERR_INVALID;
   if (!ctx->have_scene) { ctx->err = "no scene"; return IZPI_ERR_NO_SCENE; }
+  if (session_open(ctx)) return IZPI_ERR_INVALID;  // (it zeroes the counters a session keeps)
   if (n == 0) return IZPI_OK;
   HIP_TRY(hipSetDevice(ctx->device));
   DevBufs tmp;  // freed on every return
@@ -1399,6 +1609,7 @@ izpi_ctx* izpi_gpu_multi_context(izpi_multi* m, uint32_t i) { return (m && i < m
 
 int izpi_gpu_multi_upload_scene(izpi_multi* m, const izpi_scene_desc* scene) {
   if (!m) return IZPI_ERR_INVALID;
+  if (multi_session_open(m)) return IZPI_ERR_INVALID;
   PackedScene ps;  // packed once (after the first context's checks); replicated per GPU
   for (size_t i = 0; i < m->ctx.size(); i++) {
     izpi_ctx* c = m->ctx[i];
@@ -1415,6 +1626,7 @@ int izpi_gpu_multi_upload_scene(izpi_multi* m, const izpi_scene_desc* scene) {
 
 int izpi_gpu_multi_render(izpi_multi* m, const izpi_render_req* req, double* out_host, izpi_render_stats* stats) {
   if (!m || m->ctx.empty()) return IZPI_ERR_INVALID;
+  if (multi_session_open(m)) return IZPI_ERR_INVALID;
   izpi_ctx* root = m->ctx[0];
   Shares sh;
   int rc = multi_shares(m, req, sh);
@@ -1457,6 +1669,7 @@ int izpi_gpu_multi_render(izpi_multi* m, const izpi_render_req* req, double* out
 int izpi_gpu_multi_prepare(izpi_multi* m, const izpi_render_req* req) {
   if (!m || m->ctx.empty()) return IZPI_ERR_INVALID;
   if (!req) { m->err = "null argument"; return IZPI_ERR_INVALID; }
+  if (multi_session_open(m)) return IZPI_ERR_INVALID;
   Shares sh;
   const int rc = multi_shares(m, req, sh);
   if (rc) return rc;
@@ -1465,6 +1678,109 @@ int izpi_gpu_multi_prepare(izpi_multi* m, const izpi_render_req* req) {
     const int r = share_buffers(c, sh, false);
     return r ? r : render_share(c, req, sh, i, true);
   });
+}
+
+// A progressive session over the devices: izpi_gpu_multi_render's share plan, one session per
+// device over its share's units (packed; a device without units has none).
+int izpi_gpu_multi_progressive_begin(izpi_multi* m, const izpi_render_req* req, uint32_t step_spp) {
+  if (!m || m->ctx.empty()) return IZPI_ERR_INVALID;
+  if (m->prog_open) { m->err = "a progressive session is already open"; return IZPI_ERR_INVALID; }
+  if (!req || step_spp == 0) { m->err = "progressive_begin: a request and step_spp >= 1"; return IZPI_ERR_INVALID; }
+  for (izpi_ctx* c : m->ctx)
+    if (c->session.open) { m->err = "a context of this group has a progressive session of its own"; return IZPI_ERR_INVALID; }
+  int rc = session_copy_request(m->session, req, m->err);
+  if (rc) return rc;
+  izpi_ctx::Session& ms = m->session;
+  if (ms.req.spp == 0) { m->err = "invalid render request"; return IZPI_ERR_INVALID; }
+  if (ms.req.post != IZPI_POST_NONE && ms.req.num_tiles != 0) {
+    m->err = "post-processing needs a whole-frame request";
+    return IZPI_ERR_INVALID;
+  }
+  ms.step_spp = std::min(step_spp, ms.req.spp);
+  Shares sh;
+  if ((rc = multi_shares(m, &ms.req, sh))) return rc;
+  rc = on_every_device(m, [&](uint32_t i, izpi_ctx* c) {
+    const int r = share_buffers(c, sh, false);
+    if (r) return r;
+    const std::vector<uint32_t> mine = sh.mine(i);
+    if (mine.empty()) return (int)IZPI_OK;  // more shares than units
+    izpi_render_req q = ms.req;
+    q.num_tiles = (uint32_t)(mine.size() / 4);
+    q.tiles = mine.data();
+    q.out_layout = IZPI_OUT_PACKED;
+    q.post = IZPI_POST_NONE;
+    return session_begin(c, &q, ms.step_spp);
+  });
+  if (rc) {
+    for (izpi_ctx* c : m->ctx) session_drop(c);
+    return rc;
+  }
+  m->shares = sh;
+  m->prog_open = true;
+  return IZPI_OK;
+}
+
+int izpi_gpu_multi_progressive_step(izpi_multi* m, uint32_t spp, izpi_render_stats* stats) {
+  if (!m || m->ctx.empty()) return IZPI_ERR_INVALID;
+  if (!m->prog_open) { m->err = "no progressive session is open"; return IZPI_ERR_INVALID; }
+  izpi_ctx::Session& ms = m->session;
+  const uint32_t n = std::min(spp ? spp : ms.step_spp, ms.req.spp - ms.done);
+  int rc = IZPI_OK;
+  if (n) rc = on_every_device(m, [&](uint32_t, izpi_ctx* c) { return c->session.open ? session_step(c, n, nullptr) : (int)IZPI_OK; });
+  for (size_t i = 0; stats && i < m->ctx.size(); i++) stats[i] = m->ctx[i]->session.cum;
+  if (rc) return rc;
+  ms.done += n;
+  return IZPI_OK;
+}
+
+int izpi_gpu_multi_progressive_snapshot(izpi_multi* m, uint32_t form, double* out_host) {
+  if (!m || m->ctx.empty()) return IZPI_ERR_INVALID;
+  if (!m->prog_open) { m->err = "no progressive session is open"; return IZPI_ERR_INVALID; }
+  const izpi_ctx::Session& ms = m->session;
+  if (form != IZPI_SNAP_CANVAS && form != IZPI_SNAP_DISPLAY) { m->err = "unknown snapshot form"; return IZPI_ERR_INVALID; }
+  if (ms.done == 0) { m->err = "snapshot before the session's first sample"; return IZPI_ERR_INVALID; }
+  izpi_ctx* root = m->ctx[0];
+  const Shares& sh = m->shares;
+  const size_t canvas_bytes = (size_t)ms.req.width * ms.req.height * 4 * sizeof(double);
+  if (hipSetDevice(root->device) != hipSuccess) { m->err = "hipSetDevice"; return IZPI_ERR_HIP; }
+  // the caller's canvas is the starting point, as in izpi_gpu_multi_render
+  if (out_host) {
+    if (hipMemcpy(root->d_out, out_host, canvas_bytes, hipMemcpyHostToDevice) != hipSuccess) { m->err = "hipMemcpy"; return IZPI_ERR_HIP; }
+  } else if (hipMemset(root->d_out, 0, canvas_bytes) != hipSuccess) {
+    m->err = "hipMemset";
+    return IZPI_ERR_HIP;
+  }
+  // every device resolves its sums into its packed share, then copies it into its block of
+  // the root's gather buffer
+  int rc = on_every_device(m, [&](uint32_t i, izpi_ctx* c) {
+    if (!c->session.open) return (int)IZPI_OK;
+    const int r = session_snapshot(c, form, c->d_share);
+    if (r) return r;
+    hipError_t e = hipMemcpyPeerAsync(root->d_gather + (size_t)i * sh.block, root->device, c->d_share, c->device,
+                                      sh.block * sizeof(double), c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) { c->err = std::string("gather copy: ") + hipGetErrorString(e); return (int)IZPI_ERR_HIP; }
+    return (int)IZPI_OK;
+  });
+  if (rc) return rc;
+  if (hipSetDevice(root->device) != hipSuccess) { m->err = "hipSetDevice"; return IZPI_ERR_HIP; }
+  izpi_render_req q = ms.req;
+  if (form != IZPI_SNAP_CANVAS) q.post = IZPI_POST_NONE;  // the display pixels are not post-processed
+  if ((rc = assemble(root, &q, sh, root->d_out))) { m->err = root->err; return rc; }
+  if (out_host && hipMemcpy(out_host, root->d_out, canvas_bytes, hipMemcpyDeviceToHost) != hipSuccess) {
+    m->err = "hipMemcpy";
+    return IZPI_ERR_HIP;
+  }
+  return IZPI_OK;
+}
+
+int izpi_gpu_multi_progressive_end(izpi_multi* m) {
+  if (!m) return IZPI_ERR_INVALID;
+  if (!m->prog_open) { m->err = "no progressive session is open"; return IZPI_ERR_INVALID; }
+  for (izpi_ctx* c : m->ctx) session_drop(c);
+  m->session = izpi_ctx::Session{};
+  m->prog_open = false;
+  return IZPI_OK;
 }
 
 // ------------------------------------------ multi-GPU, one process per GPU
@@ -1601,6 +1917,7 @@ int izpi_gpu_render_rank(izpi_ctx* ctx, const izpi_render_req* req, double* out_
   if (!ctx) return IZPI_ERR_INVALID;
   // without a communicator no collective can run: every rank in this state returns here
   if (!ctx->comm || !ctx->d_status) { ctx->err = "render_rank before izpi_gpu_comm_init"; return IZPI_ERR_INVALID; }
+  if (session_open(ctx)) return IZPI_ERR_INVALID;  // (the caller's error on every rank alike: no collective has started)
   memset(&ctx->last, 0, sizeof(ctx->last));
   ctx->prog_done.store(0, std::memory_order_relaxed);  // (no stale count while the ranks agree)
   ctx->prog_total.store(0, std::memory_order_relaxed);
@@ -1705,6 +2022,7 @@ int izpi_gpu_multi_progress(izpi_multi* m, uint64_t* samples_done, uint64_t* sam
 
 int izpi_gpu_debug_realloc(izpi_ctx* ctx, uint32_t mask) {
   if (!ctx) return IZPI_ERR_INVALID;
+  if (session_open(ctx)) return IZPI_ERR_INVALID;  // (the fresh buffers are not copies: the sums would be lost)
   HIP_TRY(hipSetDevice(ctx->device));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   struct { void** p; size_t cap; } bufs[] = {{(void**)&ctx->d_samples, ctx->samples_cap}, {(void**)&ctx->d_recs, ctx->recs_cap},

@@ -1436,6 +1436,25 @@ struct AccumParams {
   double* running;        // [num_pixels][3]
   double* out;
 };
+// The samples one run of the chunk loops renders (run_chunks, run_preview). A one-shot render:
+// [0, req->spp), and the chunk that ends it divides and scatters (AccumParams::last). A step
+// of a progressive session: [begin, end) with keep set: every chunk is folded into the running
+// sums with last = 0, and k_resolve reads them.
+struct SampleRange {
+  uint32_t begin, end;
+  bool keep;
+};
+// k_resolve (resolve.hip): a snapshot of the running sums after `done` samples, in the
+// layout of k_accumulate's last chunk. The sums are read only.
+struct ResolveParams {
+  uint32_t num_pixels, done, width, height, tile_w, tile_h, sampler, out_layout;
+  uint32_t form;    // IZPI_SNAP_*
+  double exposure;  // IZPI_SNAP_DISPLAY of the Spectral sampler
+  const uint32_t* tiles;
+  const double* running;  // [num_pixels][3]
+  double* out;
+};
+void launch_resolve(hipStream_t st, const ResolveParams& rp);
 // ================================================================ host side
 // Scratch device buffers of one ABI call, freed when it returns (on every path).
 struct DevBufs {
@@ -1522,6 +1541,25 @@ struct izpi_ctx {
   // Progress of the running render (izpi_gpu_progress, read from other threads): samples
   // whose paths have finished, as of the host's last queue poll, and the request's samples.
   std::atomic<uint64_t> prog_done{0}, prog_total{0};
+  // The progressive session of this context (izpi_gpu_progressive_*), when open: the
+  // library's copy of the request (req.spp is the cap N; its arrays are the vectors here),
+  // the samples done, and the statistics summed over the steps. `range` is what render_body
+  // renders while the session drives it (null for a one-shot render).
+  struct Session {
+    bool open = false;
+    bool broken = false;  // a step failed: the sums are not those of `done` samples
+    izpi_render_req req{};
+    izpi_render_tuning tuning{};
+    std::vector<uint32_t> tiles;  // the request's own list (may be empty: the whole frame)
+    std::vector<double> bg_wl, bg_val;
+    uint32_t step_spp = 0, done = 0;
+    // filled by render_body: the tiles rendered, their extent and pixels
+    std::vector<uint32_t> run_tiles;
+    uint32_t tile_w = 0, tile_h = 0, num_pixels = 0;
+    izpi_render_stats cum{};
+  } session;
+  const SampleRange* range = nullptr;
+  uint32_t size_spp = 0;  // with `range`: the samples the workspace is sized for (step_spp)
 };
 
 // The words of d_misc lie MISC_STRIDE words (256 B) apart: the unit head and the queue
@@ -1575,7 +1613,7 @@ void launch_trace(izpi_ctx* ctx, const DevScene& sc, const Tracer& t, const Wave
 template <int SAMPLER, bool FWD>
 int run_sampler(izpi_ctx* ctx, const izpi_render_req* req, const DevScene& sc, const Tracer& tr, ShadeParams& sp,
                 WaveParams& wp, AccumParams& ap, uint32_t num_pixels, uint32_t chunk, uint32_t pool_blocks, bool compact,
-                float* trace_ms, float* shade_ms, float* tail_ms, uint32_t* launches);
+                const SampleRange& sr, float* trace_ms, float* shade_ms, float* tail_ms, uint32_t* launches);
 // shade_*.hip: load the code of the shading kernels run_sampler<SAMPLER, FWD> would launch
 // for the uploaded scene (izpi_gpu_upload_scene, ahead of the first frame).
 template <int SAMPLER, bool FWD>
@@ -1594,8 +1632,8 @@ struct PreviewParams {
   uint32_t slots;         // entries of buf
 };
 int run_preview(izpi_ctx* ctx, const izpi_render_req* req, const DevScene& sc, const Tracer& tr, ShadeParams& sp,
-                const PreviewParams& pp, AccumParams& ap, uint32_t num_pixels, uint32_t chunk, float* trace_ms,
-                float* shade_ms, uint32_t* launches);
+                const PreviewParams& pp, AccumParams& ap, uint32_t num_pixels, uint32_t chunk, const SampleRange& sr,
+                float* trace_ms, float* shade_ms, uint32_t* launches);
 // preview.hip: load the code of the preview kernels (izpi_gpu_upload_scene)
 int prepare_preview(izpi_ctx* ctx);
 inline bool preview_sampler(uint32_t s) {

@@ -7,6 +7,12 @@
 //               [--accumulation forward|recursive] [--out image.pfm] [--raw canvas.f64]
 //               [--device 0 | --gpus N] [--seed 12345]
 //               [--sampler colour|normal|wireframe|albedo|spectral] [--ink r,g,b]
+//               [--progressive STEP [--snapshots PREFIX]]
+//
+// --progressive STEP renders the frame in steps of STEP samples per pixel (a progressive
+// session, izpi_gpu_progressive_*) and --snapshots PREFIX writes PREFIX_<done>.pfm after each
+// step; --out / --raw get the last snapshot, byte for byte the files the same command writes
+// without --progressive.
 //
 // Defaults are the Go shim's: the GPU-built tree and the forward accumulation
 // (IZPI_ACC_FORWARD; --accumulation recursive is bit-identical to the CPU oracle).
@@ -55,10 +61,25 @@ std::string dir_of(const std::string& p) {
 // -(60 * math.Pi / 180) as Go evaluates the constant expression: pi/3 rounded once
 constexpr double kMinus60Deg = -0x1.0c152382d7366p+0;  // == -ingest.go_radians(60) (test_ingest.py)
 
+// PFM: "PF", W H, -1 (little endian), rows bottom to top
+void write_pfm(const std::string& path, const std::vector<double>& canvas, uint32_t W, uint32_t H) {
+  FILE* f = fopen(path.c_str(), "wb");
+  if (!f) die("cannot write " + path);
+  fprintf(f, "PF\n%u %u\n-1.0\n", W, H);
+  std::vector<float> row(3 * (size_t)W);
+  for (uint32_t y = H; y-- > 0;) {
+    for (uint32_t x = 0; x < W; x++)
+      for (int c = 0; c < 3; c++) row[3 * x + c] = (float)canvas[((size_t)y * W + x) * 4 + c];
+    fwrite(row.data(), sizeof(float), row.size(), f);
+  }
+  fclose(f);
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
-  std::string scene_path, obj_path, obj_material = "White", out_pfm, out_raw, bvh = "gpu", acc = "forward", sampler_name;
+  std::string scene_path, obj_path, obj_material = "White", out_pfm, out_raw, bvh = "gpu", acc = "forward", sampler_name, snap_prefix;
+  uint32_t progressive = 0;
   double ink[3] = {0.0, 0.0, 0.0};
   bool quantized = false;
   uint32_t W = 1024, H = 1024, spp = 16, depth = 50, device = 0, gpus = 1;
@@ -84,12 +105,15 @@ int main(int argc, char** argv) {
     else if (a == "--gpus") gpus = (uint32_t)atoi(val().c_str());
     else if (a == "--seed") seed = strtoull(val().c_str(), nullptr, 10);
     else if (a == "--sampler") sampler_name = val();
+    else if (a == "--progressive") { progressive = (uint32_t)atoi(val().c_str()); if (!progressive) die("--progressive takes a step of at least 1 sample"); }
+    else if (a == "--snapshots") snap_prefix = val();
     else if (a == "--ink") { if (sscanf(val().c_str(), "%lf,%lf,%lf", &ink[0], &ink[1], &ink[2]) != 3) die("--ink takes r,g,b"); }
     else die("unknown option " + a);
   }
   if (scene_path.empty()) die("--scene is required");
   if (bvh != "gpu" && bvh != "reference") die("--bvh must be gpu or reference");
   if (acc != "forward" && acc != "recursive") die("--accumulation must be forward or recursive");
+  if (!snap_prefix.empty() && !progressive) die("--snapshots needs --progressive");
   // ---- scene file (leader.go:54-75)
   std::vector<char> text;
   if (!read_file(scene_path, text)) die("cannot read " + scene_path);
@@ -186,7 +210,20 @@ int main(int argc, char** argv) {
   std::vector<double> canvas((size_t)W * H * 4);
   std::vector<izpi_render_stats> stv(gpus > 1 ? gpus : 1);
   auto t1 = std::chrono::steady_clock::now();
-  if (multi) {
+  if (progressive) {
+    // the frame in steps; a snapshot after each (the last one is the frame)
+    auto ok = [&](int r) { if (r) die(multi ? izpi_gpu_multi_last_error(multi) : izpi_gpu_last_error(ctx)); };
+    ok(multi ? izpi_gpu_multi_progressive_begin(multi, &req, progressive) : izpi_gpu_progressive_begin(ctx, &req, progressive));
+    for (uint32_t done = 0; done < spp;) {
+      ok(multi ? izpi_gpu_multi_progressive_step(multi, 0, stv.data()) : izpi_gpu_progressive_step(ctx, 0, stv.data()));
+      done = done + progressive < spp ? done + progressive : spp;
+      if (snap_prefix.empty() && done < spp) continue;
+      ok(multi ? izpi_gpu_multi_progressive_snapshot(multi, IZPI_SNAP_CANVAS, canvas.data())
+               : izpi_gpu_progressive_snapshot(ctx, IZPI_SNAP_CANVAS, canvas.data()));
+      if (!snap_prefix.empty()) write_pfm(snap_prefix + "_" + std::to_string(done) + ".pfm", canvas, W, H);
+    }
+    ok(multi ? izpi_gpu_multi_progressive_end(multi) : izpi_gpu_progressive_end(ctx));
+  } else if (multi) {
     if (izpi_gpu_multi_render(multi, &req, canvas.data(), stv.data())) die(izpi_gpu_multi_last_error(multi));
   } else if (izpi_gpu_render(ctx, &req, canvas.data(), stv.data())) {
     die(izpi_gpu_last_error(ctx));
@@ -204,18 +241,7 @@ int main(int argc, char** argv) {
     if (!f || fwrite(canvas.data(), sizeof(double), canvas.size(), f) != canvas.size()) die("cannot write " + out_raw);
     fclose(f);
   }
-  if (!out_pfm.empty()) {  // PFM: "PF", W H, -1 (little endian), rows bottom to top
-    FILE* f = fopen(out_pfm.c_str(), "wb");
-    if (!f) die("cannot write " + out_pfm);
-    fprintf(f, "PF\n%u %u\n-1.0\n", W, H);
-    std::vector<float> row(3 * (size_t)W);
-    for (uint32_t y = H; y-- > 0;) {
-      for (uint32_t x = 0; x < W; x++)
-        for (int c = 0; c < 3; c++) row[3 * x + c] = (float)canvas[((size_t)y * W + x) * 4 + c];
-      fwrite(row.data(), sizeof(float), row.size(), f);
-    }
-    fclose(f);
-  }
+  if (!out_pfm.empty()) write_pfm(out_pfm, canvas, W, H);
   if (multi) izpi_gpu_multi_close(multi);
   else izpi_gpu_close(ctx);
   izpi_host_scene_free(host);

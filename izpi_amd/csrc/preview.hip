@@ -111,8 +111,8 @@ void launch_preview(hipStream_t st, const DevScene& sc, const ShadeParams& sp, c
 }  // namespace
 
 int run_preview(izpi_ctx* ctx, const izpi_render_req* req, const DevScene& sc, const Tracer& tr, ShadeParams& sp,
-                const PreviewParams& pp, AccumParams& ap, uint32_t num_pixels, uint32_t chunk, float* trace_ms,
-                float* shade_ms, uint32_t* launches) {
+                const PreviewParams& pp, AccumParams& ap, uint32_t num_pixels, uint32_t chunk, const SampleRange& sr,
+                float* trace_ms, float* shade_ms, uint32_t* launches) {
   hipStream_t st = ctx->stream;
   if ((uint32_t)tr.blocks * 4 > ctx->num_cus * CPART_BLOCKS_PER_CU * 4) {
     ctx->err = "grid larger than the counter rows";
@@ -126,8 +126,8 @@ int run_preview(izpi_ctx* ctx, const izpi_render_req* req, const DevScene& sc, c
   wp.in_count = count; wp.trace_next = cursor; wp.slots = pp.slots;
   wp.hit_uv = pp.buf.huv ? 1u : 0u;
   wp.cpart = ctx->d_cpart;
-  for (uint32_t s0 = 0; s0 < req->spp; s0 += chunk) {
-    const uint32_t cs = std::min(chunk, req->spp - s0);
+  for (uint32_t s0 = sr.begin; s0 < sr.end; s0 += chunk) {
+    const uint32_t cs = std::min(chunk, sr.end - s0);
     sp.chunk_spp = cs; sp.s0 = s0; sp.total_units = num_pixels * cs;
     for (uint32_t base = 0; base < sp.total_units; base += pp.slots) {
       const uint32_t n = std::min(pp.slots, sp.total_units - base);
@@ -163,7 +163,7 @@ int run_preview(izpi_ctx* ctx, const izpi_render_req* req, const DevScene& sc, c
     }
     ap.chunk_spp = cs;
     ap.raw_spectral = 0;
-    ap.last = (s0 + cs >= req->spp) ? 1u : 0u;
+    ap.last = (!sr.keep && s0 + cs >= sr.end) ? 1u : 0u;
     hipLaunchKernelGGL(k_accumulate, dim3((num_pixels + 255) / 256), dim3(256), 0, st, ap);
     HIP_TRY(hipGetLastError());
   }

@@ -1001,7 +1001,7 @@ static __global__ void __launch_bounds__(256) k_accumulate(const AccumParams ap)
 template <int SAMPLER, int MATSET, bool FWD>
 int run_chunks(izpi_ctx* ctx, const izpi_render_req* req, const DevScene& sc, const Tracer& tr, ShadeParams& sp,
                WaveParams& wp, AccumParams& ap, uint32_t num_pixels, uint32_t chunk, uint32_t pool_blocks,
-               float* trace_ms, float* shade_ms, float* tail_ms, uint32_t* launches) {
+               const SampleRange& sr, float* trace_ms, float* shade_ms, float* tail_ms, uint32_t* launches) {
   hipStream_t st = ctx->stream;
   const izpi_render_tuning& tu = tuning_of(req);
   int shade_res = 0;
@@ -1054,8 +1054,8 @@ int run_chunks(izpi_ctx* ctx, const izpi_render_req* req, const DevScene& sc, co
     hipLaunchKernelGGL(k_pool_init, dim3((pool_blocks + 255) / 256), dim3(256), 0, st, sp.pool_ring, pool_blocks,
                        pool_blocks / POOL_SHARDS, sp.pool_ctr);
   HIP_TRY(hipGetLastError());
-  for (uint32_t s0 = 0; s0 < req->spp; s0 += chunk) {
-    const uint32_t cs = std::min(chunk, req->spp - s0);
+  for (uint32_t s0 = sr.begin; s0 < sr.end; s0 += chunk) {
+    const uint32_t cs = std::min(chunk, sr.end - s0);
     sp.chunk_spp = cs; sp.s0 = s0; sp.total_units = num_pixels * cs;
     const uint32_t fill = std::min<uint32_t>(sp.slots, sp.total_units);
     HIP_TRY(hipMemsetD32Async(misc(ctx, 0), (int)fill, 1, st));  // unit head: k_start gives slot i unit i
@@ -1149,7 +1149,7 @@ int run_chunks(izpi_ctx* ctx, const izpi_render_req* req, const DevScene& sc, co
     }
     ap.chunk_spp = cs;
     ap.raw_spectral = FWD && SAMPLER == IZPI_SAMPLER_SPECTRAL ? 1u : 0u;
-    ap.last = (s0 + cs >= req->spp) ? 1u : 0u;
+    ap.last = (!sr.keep && s0 + cs >= sr.end) ? 1u : 0u;
     ctx->prog_done.store((uint64_t)(s0 + cs) * num_pixels, std::memory_order_relaxed);
     hipLaunchKernelGGL(k_accumulate, dim3((num_pixels + 255) / 256), dim3(256), 0, st, ap);
     HIP_TRY(hipGetLastError());
@@ -1163,8 +1163,8 @@ int run_chunks(izpi_ctx* ctx, const izpi_render_req* req, const DevScene& sc, co
 template <int SAMPLER, bool FWD>
 int run_sampler(izpi_ctx* ctx, const izpi_render_req* req, const DevScene& sc, const Tracer& tr, ShadeParams& sp,
                 WaveParams& wp, AccumParams& ap, uint32_t num_pixels, uint32_t chunk, uint32_t pool_blocks, bool compact,
-                float* trace_ms, float* shade_ms, float* tail_ms, uint32_t* launches) {
-#define IZPI_RUN(M) run_chunks<SAMPLER, M, FWD>(ctx, req, sc, tr, sp, wp, ap, num_pixels, chunk, pool_blocks, trace_ms, shade_ms, tail_ms, launches)
+                const SampleRange& sr, float* trace_ms, float* shade_ms, float* tail_ms, uint32_t* launches) {
+#define IZPI_RUN(M) run_chunks<SAMPLER, M, FWD>(ctx, req, sc, tr, sp, wp, ap, num_pixels, chunk, pool_blocks, sr, trace_ms, shade_ms, tail_ms, launches)
   const uint32_t ms = ctx->matset;
   const int set = ms == 0 ? MATSET_BASIC : (ms & ~(uint32_t)MATSET_SURF) == 0 ? MATSET_SURF : MATSET_FULL;
   // (the compact records of MATSET_CONST are the recursion's; the forward form has none)

@@ -2,6 +2,6 @@
 #include "shade.h"
 
 template int run_sampler<IZPI_SAMPLER_SPECTRAL, false>(izpi_ctx*, const izpi_render_req*, const DevScene&, const Tracer&, ShadeParams&,
-                                 WaveParams&, AccumParams&, uint32_t, uint32_t, uint32_t, bool, float*, float*, float*,
+                                 WaveParams&, AccumParams&, uint32_t, uint32_t, uint32_t, bool, const SampleRange&, float*, float*, float*,
                                  uint32_t*);
 template int prepare_sampler<IZPI_SAMPLER_SPECTRAL, false>(izpi_ctx*, bool);

@@ -109,6 +109,88 @@ def common_tiles(width, height):
     return np.frombuffer(buf, np.uint32, count=4 * n).reshape(n, 4).copy()
 
 
+class ProgressiveSession:
+    """A progressive render (izpi_gpu_progressive_*, izpi_gpu_multi_progressive_*): the
+    frame's samples in steps, the sums kept on the device, a snapshot after any step.
+    After k samples, in any split of steps, ``snapshot()`` is the canvas ``render(spp=k)``
+    returns, bit for bit, and ``stats`` holds the same counters. A context manager: leaving
+    the block (or ``close()``) ends the session, which is also how a render is cancelled.
+
+    ``done`` / ``total``: samples per pixel rendered so far, and the session's cap.
+    ``stats``: cumulative since the session began (a list per device for a multi-GPU one)."""
+
+    def __init__(self, owner, req, step_spp):
+        self._owner = owner
+        self._multi = isinstance(owner, MultiGPURenderer)
+        self._handle = owner.m if self._multi else owner.ctx
+        self._pre = "izpi_gpu_multi_progressive_" if self._multi else "izpi_gpu_progressive_"
+        self._req = req  # (the library keeps its own copy; this one sizes the snapshots)
+        self.step_spp = int(step_spp)
+        self.total = int(req.spp)
+        self.done = 0
+        self.stats = None
+        self._open = False
+        self._call("begin", C.byref(req), self.step_spp)
+        self._open = True
+
+    def _call(self, what, *args):
+        rc = getattr(N.lib(), self._pre + what)(self._handle, *args)
+        if self._multi:
+            self._owner._check(rc, self._pre + what)
+        else:
+            _check(rc, self._handle, self._pre + what)
+
+    def step(self, n=None):
+        """Render the next n samples per pixel (None: step_spp), clipped to the cap; returns `done`."""
+        G = len(self._owner.devices) if self._multi else 1
+        st = (N.RenderStats * G)()
+        self._call("step", 0 if n is None else int(n), st)
+        want = self.step_spp if n is None else int(n)
+        self.done = min(self.total, self.done + (want if want else self.step_spp))
+        self.stats = [st[i].as_dict() for i in range(G)] if self._multi else st[0].as_dict()
+        self._owner.stats = self.stats
+        return self.done
+
+    def snapshot(self, form=N.SNAP_CANVAS, out=None):
+        """The image after `done` samples, as a host array: N.SNAP_CANVAS is what render()
+        returns at spp = done (the session's layout and post); N.SNAP_DISPLAY holds
+        display.DisplayTile's pixels (B, G, R, 1.0; Spectral: ACEScg of the exposed XYZ).
+        `out` (read first, like render()'s canvas) defaults to zeros."""
+        if out is None:
+            if self._req.out_layout == N.OUT_PACKED and not self._multi:
+                out = np.zeros(N.lib().izpi_gpu_output_bytes(C.byref(self._req)) // 8, np.float64)
+            else:
+                out = np.zeros((self._req.height, self._req.width, 4), np.float64)
+        self._call("snapshot", int(form), out.ctypes.data_as(C.c_void_p))
+        return out
+
+    def snapshot_device(self, out_ptr, form=N.SNAP_CANVAS):
+        """snapshot() into device memory at `out_ptr` (single-GPU sessions)."""
+        if self._multi:
+            raise ValueError("a multi-GPU session snapshots into host memory")
+        _check(N.lib().izpi_gpu_progressive_snapshot_device(self._handle, int(form), C.c_void_p(out_ptr)), self._handle,
+               "izpi_gpu_progressive_snapshot_device")
+
+    def close(self):
+        if self._open and getattr(self._owner, "m" if self._multi else "ctx", None):
+            self._open = False
+            self._call("end")
+        self._open = False
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class GPURenderer:
     def __init__(self, scene, width, height, spp, max_depth=50, sampler=N.SAMPLER_COLOUR, background=(0.0, 0.0, 0.0),
                  spectral_background=None, device=0, seed=12345, bvh_seed=12345, host_scene=None, bvh="reference",
@@ -212,6 +294,12 @@ class GPURenderer:
         this rank's share of render_rank."""
         req = self.request(tiles, layout, None, post)
         _check(N.lib().izpi_gpu_prepare(self.ctx, C.byref(req)), self.ctx, "izpi_gpu_prepare")
+
+    def progressive(self, step_spp, total=None, tiles=None, layout=N.OUT_CANVAS, post=N.POST_NONE):
+        """Begin a progressive render of up to `total` samples per pixel (None: this
+        renderer's spp) with a workspace sized for steps of `step_spp`: a ProgressiveSession.
+        render(), prepare() and a scene upload are refused until it is closed."""
+        return ProgressiveSession(self, self.request(tiles, layout, total, post), step_spp)
 
     def progress(self):
         """(samples finished, samples of the request) of the render running on this context,
@@ -374,6 +462,19 @@ class MultiGPURenderer:
         self._check(N.lib().izpi_gpu_multi_render(self.m, C.byref(req), ptr, st), "izpi_gpu_multi_render")
         self.stats = [st[i].as_dict() for i in range(G)]
         return canvas if to_host else None
+
+    def progressive(self, step_spp, total=None, tiles=None, layout=N.OUT_CANVAS, post=N.POST_NONE):
+        """GPURenderer.progressive over all devices: each holds a session over its share."""
+        req = make_request(self.width, self.height, self.spp if total is None else int(total), self.max_depth,
+                           self.sampler, self.background, self.seed, self.exposure, self._bg, tiles, layout, post,
+                           self.tuning, self.accumulation, self.ink)
+        return ProgressiveSession(self, req, step_spp)
+
+    def progress(self):
+        """(samples finished, samples of the request) summed over the devices (izpi_gpu_multi_progress)."""
+        d, t = C.c_uint64(), C.c_uint64()
+        self._check(N.lib().izpi_gpu_multi_progress(self.m, C.byref(d), C.byref(t)), "izpi_gpu_multi_progress")
+        return d.value, t.value
 
     def prepare(self, post=N.POST_NONE):
         """izpi_gpu_multi_prepare: every device's workspace for its share, ahead of the first frame."""
