@@ -1,13 +1,19 @@
 // izpi_gpu.hip — the C ABI of the MI355X path-tracing inner loop for izpi (include/izpi_gpu.h):
-// contexts, scene upload, workspace sizing, the render call, multi-GPU (threads and RCCL ranks),
-// post-processing and the component entries. The kernels of the hot path are in trace.hip and
-// shade.hip (izpi_kern.h).
+// contexts, scene upload, the render call (its workspace is planned in render_plan.cpp), multi-GPU
+// (threads and RCCL ranks), post-processing and the component entries. The kernels of the
+// hot path are in trace.hip and shade.hip (izpi_kern.h).
 #include "izpi_kern.h"
 #include "scene_pack.h"
+
+#include <array>
 
 using izpi_internal::Double4;
 using izpi_internal::pack_scene;
 using izpi_internal::PackedScene;
+using izpi_internal::PlanCache;
+using izpi_internal::PlanInput;
+using izpi_internal::SideLayout;
+using izpi_internal::WorkspacePlan;
 
 // FireflyRejection (firefly_rejection.go:12-113) fused with XYZToRGB (rgb_image.go:28-67).
 // FireflyRejection reads only the ORIGINAL Y plane (it copies it first, :33-39) and
@@ -239,38 +245,44 @@ int grow(izpi_ctx* ctx, void** p, size_t* cap, size_t bytes) {
   return IZPI_OK;
 }
 
-// Device bytes of the render workspace (the buffers `grow` manages).
-uint64_t workspace_bytes(const izpi_ctx* ctx) {
-  return (uint64_t)ctx->samples_cap + ctx->recs_cap + ctx->pool_cap + ctx->ring_cap + ctx->running_cap + ctx->out_cap +
-         ctx->tiles_cap + ctx->utiles_cap + ctx->bg_cap + ctx->state_cap + ctx->spill_cap + ctx->post_cap + ctx->share_cap +
-         ctx->gather_cap + ctx->cpart_cap + ctx->finq_cap;
-}
-
-// Device bytes of the buffers render_impl sizes per frame and may release to re-size
-// (not the output, share, gather and post-processing buffers, which it never frees).
-uint64_t render_buffer_bytes(const izpi_ctx* ctx) {
-  return (uint64_t)ctx->samples_cap + ctx->recs_cap + ctx->pool_cap + ctx->ring_cap + ctx->running_cap + ctx->state_cap +
-         ctx->spill_cap;
-}
-
-struct RenderBuf {
+// Every device buffer `grow` manages. The first RENDER_BUFS are the ones a render sizes per
+// frame and may release to re-size (not the output, share, gather and post-processing
+// buffers, which it never frees), in the order of izpi_gpu_debug_realloc's mask bits.
+struct CtxBuf {
   void** p;
   size_t* cap;
-  size_t bytes;
 };
+constexpr size_t RENDER_BUFS = 7, CTX_BUFS = 16;
+std::array<CtxBuf, CTX_BUFS> ctx_buffers(izpi_ctx* c) {
+#define IZPI_BUF(name) CtxBuf{(void**)&c->d_##name, &c->name##_cap}
+  return {IZPI_BUF(samples), IZPI_BUF(recs), IZPI_BUF(pool), IZPI_BUF(ring), IZPI_BUF(running), IZPI_BUF(state),
+          IZPI_BUF(spill), IZPI_BUF(out), IZPI_BUF(tiles), IZPI_BUF(utiles), IZPI_BUF(bg), IZPI_BUF(post),
+          IZPI_BUF(share), IZPI_BUF(gather), IZPI_BUF(cpart), IZPI_BUF(finq)};
+#undef IZPI_BUF
+}
+uint64_t buffer_bytes(izpi_ctx* ctx, size_t n) {
+  uint64_t sum = 0;
+  const auto bufs = ctx_buffers(ctx);
+  for (size_t i = 0; i < n; i++) sum += *bufs[i].cap;
+  return sum;
+}
+// Device bytes of the render workspace, and of the buffers a render may release to re-size.
+uint64_t workspace_bytes(izpi_ctx* ctx) { return buffer_bytes(ctx, CTX_BUFS); }
+uint64_t render_buffer_bytes(izpi_ctx* ctx) { return buffer_bytes(ctx, RENDER_BUFS); }
 
-// Make every buffer of `b` at least its `bytes`: if any must grow, free them all first,
-// then allocate each at exactly its size.
-int grow_render_buffers(izpi_ctx* ctx, RenderBuf* b, size_t n, bool* fresh) {
+// Make each of the first RENDER_BUFS buffers at least its `bytes`: if any must grow, free them
+// all first, then allocate each at exactly its size.
+int grow_render_buffers(izpi_ctx* ctx, const CtxBuf* b, const size_t* bytes, bool* fresh) {
+  const size_t n = RENDER_BUFS;
   for (size_t i = 0; i < n; i++)  // a buffer this render does not use (the records of IZPI_ACC_FORWARD)
-    if (b[i].bytes == 0 && *b[i].p) {
+    if (bytes[i] == 0 && *b[i].p) {
       HIP_TRY(hipStreamSynchronize(ctx->stream));
       HIP_TRY(hipFree(*b[i].p));
       *b[i].p = nullptr;
       *b[i].cap = 0;
     }
   bool must = false;
-  for (size_t i = 0; i < n; i++) must = must || *b[i].cap < b[i].bytes;
+  for (size_t i = 0; i < n; i++) must = must || *b[i].cap < bytes[i];
   *fresh = must;
   if (!must) return IZPI_OK;
   HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -280,46 +292,34 @@ int grow_render_buffers(izpi_ctx* ctx, RenderBuf* b, size_t n, bool* fresh) {
     *b[i].cap = 0;
   }
   for (size_t i = 0; i < n; i++) {
-    if (b[i].bytes == 0) continue;
-    const hipError_t e = hipMalloc(b[i].p, b[i].bytes);
+    if (bytes[i] == 0) continue;
+    const hipError_t e = hipMalloc(b[i].p, bytes[i]);
     if (e != hipSuccess) {
       *b[i].p = nullptr;
-      ctx->err = "render workspace: hipMalloc of " + std::to_string(b[i].bytes) + " bytes: " + hipGetErrorString(e);
+      ctx->err = "render workspace: hipMalloc of " + std::to_string(bytes[i]) + " bytes: " + hipGetErrorString(e);
       return IZPI_ERR_HIP;
     }
-    *b[i].cap = b[i].bytes;
+    *b[i].cap = bytes[i];
   }
   return IZPI_OK;
 }
 
-// The two sides of the wavefront state, `slots` entries each, in one allocation:
-// returns the bytes (base == nullptr) or fills b[0], b[1].
-size_t carve_state(char* base, uint32_t slots, bool time, bool blk, bool cold, bool uv, uint32_t thr_planes, WaveBuf* b) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) -> char* {
-    char* p = base ? base + off : nullptr;
-    off += (bytes + 255) & ~(size_t)255;
-    return p;
-  };
-  for (int k = 0; k < 2; k++) {
-    WaveBuf w{};
-    w.ray = (RayOD*)take((size_t)slots * sizeof(RayOD));
-    w.kind = (uint32_t*)take((size_t)slots * sizeof(uint32_t));
-    w.time = time ? (double*)take((size_t)slots * sizeof(double)) : nullptr;
-    w.path = (PathHot*)take((size_t)slots * sizeof(PathHot));
-    w.blk = blk ? (uint32_t*)take((size_t)slots * sizeof(uint32_t)) : nullptr;
-    w.cold = cold ? (PathCold*)take((size_t)slots * sizeof(PathCold)) : nullptr;
-    // with (u, v): one 32-B record per entry, (t, prim) then (u, v), so a finished ray's
-    // two stores land in one line (two separate arrays made C4 / C5 trace 6-7% slower)
-    w.hs = uv ? 2u : 1u;
-    w.hit = (double2*)take((size_t)slots * w.hs * sizeof(double2));
-    w.huv = uv && w.hit ? w.hit + 1 : nullptr;
-    w.tminmax = nullptr;
-    w.thr = thr_planes ? (double*)take((size_t)slots * thr_planes * sizeof(double)) : nullptr;
-    w.tplane = slots;
-    if (b) b[k] = w;
-  }
-  return off;
+// One side of the wavefront state at its place in izpi_ctx::d_state.
+WaveBuf bind_side(char* base, const WorkspacePlan& plan, const SideLayout& s) {
+  auto at = [base](uint64_t off) { return off == SideLayout::ABSENT ? nullptr : base + off; };
+  WaveBuf w{};
+  w.ray = (RayOD*)at(s.ray);
+  w.kind = (uint32_t*)at(s.kind);
+  w.time = (double*)at(s.time);
+  w.path = (PathHot*)at(s.path);
+  w.blk = (uint32_t*)at(s.blk);
+  w.cold = (PathCold*)at(s.cold);
+  w.hs = plan.uv ? 2u : 1u;  // (t, prim) and (u, v) interleaved
+  w.hit = (double2*)at(s.hit);
+  w.huv = plan.uv ? w.hit + 1 : nullptr;
+  w.thr = (double*)at(s.thr);
+  w.tplane = plan.slots;
+  return w;
 }
 
 void free_scene(izpi_ctx* ctx) {
@@ -381,147 +381,17 @@ int apply_post(izpi_ctx* ctx, const izpi_render_req* req, double* canvas_dev) {
   return IZPI_OK;
 }
 
-// A step of a progressive session finds the workspace its begin allocated: were a buffer to
-// be re-allocated (`moved`), the running sums would go with it.
-int session_keeps_sums(izpi_ctx* ctx, const SampleRange& sr, bool moved) {
-  if (!sr.keep || ctx->prepare_only || !moved) return IZPI_OK;
-  ctx->err = "progressive step: the session's workspace no longer fits (its sums would be lost)";
-  return IZPI_ERR_INVALID;
-}
-
-// The preview samplers' entries, `slots` of them, in izpi_ctx::d_state: returns the bytes
-// (base == nullptr) or fills pp.buf and pp.tminmax.
-size_t carve_preview(char* base, uint32_t slots, bool time, bool uv, bool wire, PreviewParams* pp) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) -> char* {
-    char* p = base ? base + off : nullptr;
-    off += (bytes + 255) & ~(size_t)255;
-    return p;
-  };
-  WaveBuf w{};
-  w.ray = (RayOD*)take((size_t)slots * sizeof(RayOD));
-  w.kind = (uint32_t*)take((size_t)slots * sizeof(uint32_t));
-  w.time = time ? (double*)take((size_t)slots * sizeof(double)) : nullptr;
-  w.hs = uv ? 2u : 1u;  // (t, prim) and (u, v) interleaved, as carve_state
-  w.hit = (double2*)take((size_t)slots * w.hs * sizeof(double2));
-  w.huv = uv && w.hit ? w.hit + 1 : nullptr;
-  w.tplane = slots;
-  double2* tm = wire ? (double2*)take((size_t)slots * sizeof(double2)) : nullptr;
-  if (pp) { pp->buf = w; pp->tminmax = tm; pp->slots = slots; }
-  return off;
-}
-
-// render_body for the Normal, Albedo and WireFrame samplers, from the point where the
-// request is checked and its tiles and k_trace2 instance are known: a workspace of camera
-// rays, hits and per-sample results only (no records, pool, or second side of the state),
-// within the buffers a Colour render of this context may already hold (they only grow here).
-int preview_body(izpi_ctx* ctx, const izpi_render_req* req, const DevScene& sc, const Tracer& tr, const izpi_render_tuning& tu,
-                 const std::vector<uint32_t>& tiles, uint32_t tw, uint32_t th, uint32_t num_pixels, const SampleRange& sr,
-                 uint32_t size_spp, double* out_dev) {
-  const bool wire = req->sampler == IZPI_SAMPLER_WIREFRAME;
-  const bool need_time = !ctx->sc.tri_only, need_uv = !ctx->sc.tri_only || ctx->any_uv;
-  const uint64_t size_key[8] = {num_pixels, size_spp, req->sampler, tu.slots, tu.chunk_units, 0, 0, 0};
-  const bool reuse = ctx->pv_sizing_valid && memcmp(size_key, ctx->pv_sizing.key, sizeof(size_key)) == 0;
-  uint32_t chunk = ctx->pv_sizing.chunk, slots = ctx->pv_sizing.slots;
-  if (!reuse) {
-    // as render_body: per-sample results within 1/8 of the HBM this context may use, the
-    // entries within the rest of 15/32 of it
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
-    const uint64_t avail = free_b ? ((uint64_t)free_b + render_buffer_bytes(ctx)) / std::max(1u, ctx->dev_share) : 0;
-    uint64_t max_units = std::max<uint64_t>(64ull << 20, (avail / 8) / (SMP_D * sizeof(double)));
-    if (tu.chunk_units) max_units = tu.chunk_units;
-    chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(size_spp, max_units / num_pixels));
-    const uint32_t nchunks = (size_spp + chunk - 1) / chunk;
-    chunk = (size_spp + nchunks - 1) / nchunks;
-    uint64_t slot_cap = 256ull << 20;
-    if (tu.slots) slot_cap = std::max<uint64_t>(1024, tu.slots);
-    const uint64_t per_slot = carve_preview(nullptr, 1024, need_time, need_uv, wire, nullptr) / 1024 + 1;
-    const uint64_t samples_bytes = (uint64_t)num_pixels * chunk * SMP_D * sizeof(double), budget = avail / 32 * 15;
-    if (avail > 0) slot_cap = std::min<uint64_t>(slot_cap, std::max<uint64_t>(1024, (budget > samples_bytes ? budget - samples_bytes : 0) / per_slot));
-    slots = (uint32_t)std::min<uint64_t>((uint64_t)num_pixels * chunk, slot_cap);
-    memcpy(ctx->pv_sizing.key, size_key, sizeof(size_key));
-    ctx->pv_sizing.chunk = chunk; ctx->pv_sizing.slots = slots;
-    ctx->pv_sizing_valid = true;
-  }
-  const auto t_alloc0 = std::chrono::steady_clock::now();
-  const size_t samples_bytes = (size_t)num_pixels * chunk * SMP_D * sizeof(double);
-  const size_t state_bytes = carve_preview(nullptr, slots, need_time, need_uv, wire, nullptr);
-  const uint32_t cpart_rows = ctx->num_cus * CPART_BLOCKS_PER_CU * 4u;
-  int rc;
-  if ((rc = session_keeps_sums(ctx, sr, ctx->running_cap < (size_t)num_pixels * 3 * sizeof(double)))) return rc;
-  if ((rc = grow(ctx, (void**)&ctx->d_samples, &ctx->samples_cap, samples_bytes)) ||
-      (rc = grow(ctx, (void**)&ctx->d_running, &ctx->running_cap, (size_t)num_pixels * 3 * sizeof(double))) ||
-      (rc = grow(ctx, (void**)&ctx->d_state, &ctx->state_cap, state_bytes)) ||
-      (rc = grow(ctx, (void**)&ctx->d_spill, &ctx->spill_cap, tr.spill_bytes)) ||
-      (rc = grow(ctx, (void**)&ctx->d_tiles, &ctx->tiles_cap, tiles.size() * sizeof(uint32_t))) ||
-      (rc = grow(ctx, (void**)&ctx->d_cpart, &ctx->cpart_cap, (size_t)cpart_rows * CNT_N * sizeof(unsigned long long)))) {
-    ctx->pv_sizing_valid = false;
-    return rc;
-  }
-  const double alloc_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_alloc0).count();
-  hipStream_t st = ctx->stream;
-  if (ctx->prepare_only) {  // izpi_gpu_prepare: the device's first work on the workspace, as render_body
-    HIP_TRY(hipMemsetAsync(ctx->d_state, 0, state_bytes, st));
-    HIP_TRY(hipMemsetAsync(ctx->d_samples, 0, samples_bytes, st));
-    if (sr.keep) {  // izpi_gpu_progressive_begin: the session's sums and counters start at zero
-      HIP_TRY(hipMemsetAsync(ctx->d_running, 0, (size_t)num_pixels * 3 * sizeof(double), st));
-      HIP_TRY(hipMemsetAsync(ctx->d_counters, 0, CNT_N * sizeof(unsigned long long), st));
-    }
-    HIP_TRY(hipStreamSynchronize(st));
-    ctx->last = izpi_render_stats{};
-    ctx->last.workspace_bytes = workspace_bytes(ctx);
-    ctx->last.slots = slots; ctx->last.chunk_spp = chunk; ctx->last.alloc_ms = alloc_ms;
-    return IZPI_OK;
-  }
-  HIP_TRY(hipMemcpyAsync(ctx->d_tiles, tiles.data(), tiles.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  if (!sr.keep) {  // (a session's sums and counters run on from step to step)
-    HIP_TRY(hipMemsetAsync(ctx->d_running, 0, (size_t)num_pixels * 3 * sizeof(double), st));
-    HIP_TRY(hipMemsetAsync(ctx->d_counters, 0, CNT_N * sizeof(unsigned long long), st));
-  }
-  HIP_TRY(hipMemsetAsync(ctx->d_cpart, 0, (size_t)cpart_rows * CNT_N * sizeof(unsigned long long), st));
-  HIP_TRY(hipMemsetAsync(ctx->d_misc, 0, 8 * MISC_STRIDE * sizeof(uint32_t), st));
-  ShadeParams sp{};
-  sp.width = req->width; sp.height = req->height; sp.tile_w = tw; sp.tile_h = th; sp.slots = slots;
-  sp.max_depth = 1;  // (the request's is ignored; start_path completes a sample of max_depth 0 at once)
-  sp.tiles = ctx->d_tiles; sp.seed = req->seed; sp.out = ctx->d_samples;
-  sp.background[0] = req->background[0]; sp.background[1] = req->background[1]; sp.background[2] = req->background[2];
-  sp.counters = ctx->d_counters; sp.cpart = ctx->d_cpart; sp.error = misc(ctx, 1);
-  PreviewParams pp{};
-  carve_preview(ctx->d_state, slots, need_time, need_uv, wire, &pp);
-  pp.verts = ctx->d_triverts;
-  if (req->abi_version >= 4)  // (a request of ABI 3 ends before `ink`: black)
-    for (int k = 0; k < 3; k++) pp.ink[k] = req->ink[k];
-  AccumParams ap{};
-  ap.num_pixels = num_pixels; ap.spp = req->spp; ap.width = req->width; ap.height = req->height;
-  ap.tile_w = tw; ap.tile_h = th; ap.sampler = IZPI_SAMPLER_COLOUR;  // col / numSamples (rgb.go:38)
-  ap.out_layout = req->out_layout;
-  ap.tiles = ctx->d_tiles; ap.samples = ctx->d_samples; ap.running = ctx->d_running; ap.out = out_dev;
-  float trace_ms = 0, shade_ms = 0, total_ms = 0;
-  uint32_t launches = 0;
-  HIP_TRY(hipEventRecord(ctx->ev0, st));
-  if ((rc = run_preview(ctx, req, sc, tr, sp, pp, ap, num_pixels, chunk, sr, &trace_ms, &shade_ms, &launches))) return rc;
-  hipLaunchKernelGGL(k_cpart_reduce, dim3(CNT_N), dim3(256), 0, st, ctx->d_cpart, cpart_rows, ctx->d_counters);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(ctx->ev1, st));
-  if (!sr.keep && (rc = apply_post(ctx, req, out_dev))) return rc;
-  HIP_TRY(hipEventSynchronize(ctx->ev1));
-  HIP_TRY(hipEventElapsedTime(&total_ms, ctx->ev0, ctx->ev1));
-  unsigned long long cnt[CNT_N];
-  uint32_t guard = 0;
-  HIP_TRY(hipMemcpy(cnt, ctx->d_counters, sizeof(cnt), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(&guard, misc(ctx, 1), sizeof(guard), hipMemcpyDeviceToHost));
-  izpi_render_stats& s = ctx->last;
-  memset(&s, 0, sizeof(s));
-  s.rays = cnt[CNT_RAYS]; s.node_visits = cnt[CNT_NODES]; s.tri_tests = cnt[CNT_TRI]; s.sph_tests = cnt[CNT_SPH];
-  s.samples = (uint64_t)num_pixels * sr.end;
-  s.kernel_ms = trace_ms; s.shade_ms = shade_ms; s.total_ms = total_ms; s.launches = launches;
-  s.node_steps = cnt[CNT_NSTEP]; s.prim_steps = cnt[CNT_PSTEP]; s.leaf_shortcuts = cnt[CNT_SHORT];
-  s.workspace_bytes = workspace_bytes(ctx);
-  s.scene_bytes = ctx->scene_bytes;
-  s.slots = slots; s.chunk_spp = chunk; s.alloc_ms = alloc_ms;
-  if (guard) { ctx->err = "device guard: traversal stack overflow"; return IZPI_ERR_DEVICE; }
-  return IZPI_OK;
+// How a render call is driven: the samples it renders, the samples its workspace is sized
+// for (the request's, or a progressive session's step_spp: the sums then stay in d_running),
+// and whether it stops once the workspace is allocated (izpi_gpu_prepare, a session's begin).
+struct RenderCall {
+  SampleRange range;
+  uint32_t size_spp;
+  bool prepare_only;
+};
+RenderCall one_shot(const izpi_render_req* req, bool prepare_only = false) {
+  const uint32_t spp = req ? req->spp : 0;
+  return RenderCall{SampleRange{0, spp, false}, spp, prepare_only};
 }
 
 // A progressive session owns the context's running sums, counters and progress: the calls
@@ -532,39 +402,43 @@ bool session_open(izpi_ctx* ctx) {
   return true;
 }
 
-int render_body(izpi_ctx* ctx, const izpi_render_req* req, double* out_dev);
-// One render on one context. The progress counters (izpi_gpu_progress) start at 0/0 before
-// any check and read done == total on every return, failed calls included.
-int render_impl(izpi_ctx* ctx, const izpi_render_req* req, double* out_dev) {
-  if (session_open(ctx)) return IZPI_ERR_INVALID;  // (before the progress counters: they are the session's)
-  ctx->prog_done.store(0, std::memory_order_relaxed);
-  ctx->prog_total.store(0, std::memory_order_relaxed);
-  const int rc = render_body(ctx, req, out_dev);
-  ctx->prog_done.store(ctx->prog_total.load(std::memory_order_relaxed), std::memory_order_relaxed);
-  return rc;
+// A step of a progressive session finds the workspace its begin allocated: were a buffer to
+// be re-allocated (`moved`), the running sums would go with it.
+int session_keeps_sums(izpi_ctx* ctx, const RenderCall& call, bool moved) {
+  if (!call.range.keep || call.prepare_only || !moved) return IZPI_OK;
+  ctx->err = "progressive step: the session's workspace no longer fits (its sums would be lost)";
+  return IZPI_ERR_INVALID;
 }
 
-int render_body(izpi_ctx* ctx, const izpi_render_req* req, double* out_dev) {
-  const auto t_body0 = std::chrono::steady_clock::now();
-  auto host_ms = [&t_body0]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_body0).count(); };
+// counter rows: one per wave of the largest grid (run_chunks and run_preview check the grids against it)
+uint32_t cpart_rows(const izpi_ctx* ctx) { return ctx->num_cus * CPART_BLOCKS_PER_CU * 4u; }
+
+// ---- render_body's steps, shared by the path samplers and the preview samplers
+// 1. The request against the ABI and the scene; what the later steps need of it.
+struct RequestShape {
+  std::vector<uint32_t> tiles;
+  uint32_t tw = 0, th = 0, num_pixels = 0;
+  bool fwd = false;      // IZPI_ACC_FORWARD (never with a preview sampler: they ignore the accumulation, as max_depth)
+  bool preview = false;  // Normal, Albedo, WireFrame
+};
+int check_request(izpi_ctx* ctx, const izpi_render_req* req, RequestShape* rs) {
   if (ctx->fault_inject == 2) { ctx->err = "injected render fault (izpi_gpu_debug_fault)"; return IZPI_ERR_DEVICE; }
   if (!ctx->have_scene) { ctx->err = "render before izpi_gpu_upload_scene"; return IZPI_ERR_NO_SCENE; }
   if (!req || req->width == 0 || req->height == 0 || req->spp == 0) { ctx->err = "invalid render request"; return IZPI_ERR_INVALID; }
   if (req->abi_version > IZPI_ABI_VERSION) { ctx->err = "render request from a newer ABI"; return IZPI_ERR_INVALID; }
-  const bool preview = preview_sampler(req->sampler);
-  if (req->sampler != IZPI_SAMPLER_COLOUR && req->sampler != IZPI_SAMPLER_SPECTRAL && !preview) { ctx->err = "unsupported sampler"; return IZPI_ERR_UNSUPPORTED; }
+  rs->preview = preview_sampler(req->sampler);
+  if (req->sampler != IZPI_SAMPLER_COLOUR && req->sampler != IZPI_SAMPLER_SPECTRAL && !rs->preview) { ctx->err = "unsupported sampler"; return IZPI_ERR_UNSUPPORTED; }
   // (a request of ABI 1 or 2 ends at `tuning`: accumulation is not read)
-  // (the preview samplers ignore it, as they ignore max_depth)
-  const uint32_t acc = preview ? (uint32_t)IZPI_ACC_RECURSIVE : req->abi_version >= 3 ? req->accumulation : (uint32_t)IZPI_ACC_RECURSIVE;
+  const uint32_t acc = rs->preview ? (uint32_t)IZPI_ACC_RECURSIVE : req->abi_version >= 3 ? req->accumulation : (uint32_t)IZPI_ACC_RECURSIVE;
   if (acc != IZPI_ACC_RECURSIVE && acc != IZPI_ACC_FORWARD) { ctx->err = "unknown accumulation mode"; return IZPI_ERR_INVALID; }
-  const bool fwd = acc == IZPI_ACC_FORWARD;
+  rs->fwd = acc == IZPI_ACC_FORWARD;
   if (req->post != IZPI_POST_NONE &&
       ((req->post & ~(uint32_t)(IZPI_POST_SPECTRAL | IZPI_POST_GAMMA_CLAMP)) || req->out_layout != IZPI_OUT_CANVAS ||
        req->num_tiles != 0)) {
     ctx->err = "post-processing needs a whole-frame IZPI_OUT_CANVAS request";
     return IZPI_ERR_INVALID;
   }
-  if (preview && (req->post & IZPI_POST_SPECTRAL)) {
+  if (rs->preview && (req->post & IZPI_POST_SPECTRAL)) {
     ctx->err = "IZPI_POST_SPECTRAL needs the Spectral sampler's XYZ canvas";
     return IZPI_ERR_INVALID;
   }
@@ -575,277 +449,290 @@ int render_body(izpi_ctx* ctx, const izpi_render_req* req, double* out_dev) {
     ctx->err = "a material lacks the textures this sampler reads";
     return IZPI_ERR_INVALID;
   }
-  if (!preview && ctx->sc.num_lights == 0) { ctx->err = "scene has no lights (HitableSlice.PDFValue divides by zero)"; return IZPI_ERR_INVALID; }
-  std::vector<uint32_t> tiles;
-  int rc = request_tiles(ctx, req, tiles);
+  if (!rs->preview && ctx->sc.num_lights == 0) { ctx->err = "scene has no lights (HitableSlice.PDFValue divides by zero)"; return IZPI_ERR_INVALID; }
+  const int rc = request_tiles(ctx, req, rs->tiles);
   if (rc) return rc;
-  uint32_t tw = 0, th = 0;
-  const uint32_t ntiles = validate_tiles(req, tiles.data(), (uint32_t)(tiles.size() / 4), &tw, &th);
+  const uint32_t ntiles = validate_tiles(req, rs->tiles.data(), (uint32_t)(rs->tiles.size() / 4), &rs->tw, &rs->th);
   if (ntiles == 0) { ctx->err = "tiles must be non-empty, in bounds and equal-sized"; return IZPI_ERR_INVALID; }
-  const uint64_t num_pixels64 = (uint64_t)ntiles * tw * th;
+  const uint64_t num_pixels64 = (uint64_t)ntiles * rs->tw * rs->th;
   if (num_pixels64 > (1ull << 30)) { ctx->err = "too many pixels in one request"; return IZPI_ERR_INVALID; }
-  const uint32_t num_pixels = (uint32_t)num_pixels64;
+  rs->num_pixels = (uint32_t)num_pixels64;
   ctx->prog_total.store(num_pixels64 * req->spp, std::memory_order_relaxed);
-  // The samples this call renders and the samples its workspace is sized for: the request's,
-  // or a progressive session's step and its step_spp (the sums then stay in d_running).
-  const SampleRange sr = ctx->range ? *ctx->range : SampleRange{0, req->spp, false};
-  const uint32_t size_spp = ctx->range ? ctx->size_spp : req->spp;
-  if (sr.keep) {
-    izpi_ctx::Session& ss = ctx->session;
-    ss.run_tiles = tiles; ss.tile_w = tw; ss.tile_h = th; ss.num_pixels = num_pixels;
-  }
   if (ctx->stack_needed > 64) { ctx->err = "BVH deeper than the 64-entry traversal stack (bvh4.go:71)"; return IZPI_ERR_UNSUPPORTED; }
-  const izpi_render_tuning& tu = tuning_of(req);
-  // this render's view of the scene: the traversal shortcuts the tuning switches off
-  DevScene sc = ctx->sc;
-  if (tu.flags & IZPI_TUNE_NO_LEAF_SHORTCUT) sc.leaf_shortcut = 0;
-  if (tu.flags & IZPI_TUNE_SCALAR_SLAB) sc.nan_free_bounds = 0;
-  Tracer tr;
-  const double t_tiles = host_ms();
-  int trc = make_tracer(ctx, tu, !ctx->sc.tri_only || ctx->any_uv, &tr);
-  if (trc) return trc;
-  if (tu.flags & IZPI_TUNE_PASS_LOG)  // diagnostics: the k_trace2 instance this render runs
-    fprintf(stderr, "IZPI_TRACE_INSTANCE dist=%d tri=%d lds_bvh=%d ray_lds=%d q=%d\n", (int)tr.p2, (int)tr.tri, (int)tr.lds_bvh,
-            (int)tr.ray_lds, (int)tr.qnodes);
-  const double t_tracer = host_ms();
-  if (preview) return preview_body(ctx, req, sc, tr, tu, tiles, tw, th, num_pixels, sr, size_spp, out_dev);
-  // Sizing against the HBM this context may use: what is free plus the render buffers it
-  // holds and would release (a later frame reuses them, so every frame of a renderer sizes
-  // alike), shared evenly by the contexts of one process on this device.
-  const uint64_t size_key[8] = {num_pixels, size_spp, req->sampler, req->max_depth, ctx->pool_grow,
-                                ((uint64_t)tu.slots << 32) | tu.chunk_units, ((uint64_t)tu.rec_dense << 32) | tu.pool_div, acc};
-  const bool reuse = ctx->sizing_valid && memcmp(size_key, ctx->sizing.key, sizeof(size_key)) == 0;
+  return IZPI_OK;
+}
+
+// 2. What plan_workspace reads of this call (render_plan.h), but for `avail`. The preview
+// samplers' plans do not depend on the fields they ignore.
+PlanInput plan_input(const izpi_ctx* ctx, const izpi_render_req* req, const RequestShape& rs, const izpi_render_tuning& tu,
+                     uint32_t size_spp) {
+  PlanInput in{};
+  in.num_pixels = rs.num_pixels; in.size_spp = size_spp; in.sampler = req->sampler;
+  in.slots = tu.slots; in.chunk_units = tu.chunk_units;
+  in.tri_only = ctx->sc.tri_only; in.any_uv = ctx->any_uv;
+  if (!rs.preview) {
+    in.accumulation = rs.fwd ? IZPI_ACC_FORWARD : IZPI_ACC_RECURSIVE; in.max_depth = req->max_depth;
+    in.rec_dense = tu.rec_dense; in.pool_div = tu.pool_div; in.pool_grow = ctx->pool_grow;
+    in.no_pathlen = ctx->sc.no_pathlen; in.const_basic = ctx->basic_materials && ctx->const_albedo;
+  }
+  return in;
+}
+// The HBM this context may use: what is free plus the render buffers it holds and would
+// release (a later frame reuses them, so every frame of a renderer sizes alike), shared
+// evenly by the contexts of one process on this device. 0: the reading failed.
+uint64_t available_bytes(izpi_ctx* ctx) {
   size_t free_b = 0, total_b = 0;
-  if (!reuse && hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
-  const double t_meminfo = host_ms();
-  const uint64_t avail = free_b ? ((uint64_t)free_b + render_buffer_bytes(ctx)) / std::max(1u, ctx->dev_share) : 0;
-  // The render workspace stays within 15/32 of the HBM (~135 GB of 288, under the ~137 GB
-  // C3 takes at its slot cap): per-sample results within 1/8, the wavefront state in the
-  // rest. At 17/32 C4 took 153 GB, and a fresh process allocating it right after processes
-  // of ~131-137 GB waited 0.4-3.9 s for the driver to clear VRAM (first frame up to 6.6x
-  // steady); at 113 GB it allocated in 2 ms and its steady frame was 0.7% slower.
-  // Per-sample results wait in HBM ([units][3] doubles) until k_accumulate folds them in
-  // sample order. One chunk per request when it fits in 1/8 of the HBM (C3: 12.9 GB of
-  // 288 GB), so the wavefront drains once per frame instead of once per chunk (C4 at 1024
-  // spp: 2 chunks, C5 at 4096 spp: 12; a chunk's drain costs a few ms).
-  uint64_t max_units = std::max<uint64_t>(64ull << 20, (avail / 8) / (3 * sizeof(double)));
-  if (tu.chunk_units) max_units = tu.chunk_units;
-  // the chunks of a request are balanced: as many as the limit needs, equal in size (C4 at
-  // 1024 spp: 2 chunks of 512 instead of 774 + 250, 13 GB less to allocate, same drains)
-  uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(size_spp, max_units / num_pixels));
-  const uint32_t nchunks = (size_spp + chunk - 1) / chunk;
-  chunk = (size_spp + nchunks - 1) / nchunks;
-  if (reuse) chunk = ctx->sizing.chunk;
-  // Unwinding records: the first rec_dense levels per slot, deeper levels in overflow
-  // blocks (ShadeParams::rec_pool). Colour records are 40 B (24 B compact), spectral 24 B.
-  const bool spectral = req->sampler == IZPI_SAMPLER_SPECTRAL;
-  const bool compact = !fwd && !spectral && ctx->basic_materials && ctx->const_albedo;
-  const uint32_t D = spectral  ? RecLayout<IZPI_SAMPLER_SPECTRAL, MATSET_FULL>::D
-                     : compact ? RecLayout<IZPI_SAMPLER_COLOUR, MATSET_CONST>::D
-                               : RecLayout<IZPI_SAMPLER_COLOUR, MATSET_FULL>::D;
-  const uint32_t max_depth = std::max(1u, req->max_depth);
-  // Spectral glass paths run deep (C5: 12 rays per sample): with 16 dense levels the first
-  // frame parked 15% of its shading items on an empty overflow pool; 32 levels park none
-  // (C5 256 spp first frame 8854 -> 8130 ms; 92 GB of workspace, less than a pool twice the
-  // size would take).
-  uint32_t rec_dense = spectral ? 32u : 8u;
-  if (tu.rec_dense) rec_dense = tu.rec_dense;
-  rec_dense = std::min(rec_dense, max_depth);
-  if (fwd) rec_dense = max_depth;  // (no records at all: see need[] and the pool below)
-  const uint32_t rec_pool = max_depth - rec_dense;
-  // IZPI_ACC_FORWARD: the throughput per entry instead of the records (3 planes Colour, 1 Spectral)
-  const uint32_t thr_planes = fwd ? (spectral ? 1u : 3u) : 0u;
-  const uint64_t rec_bytes_slot = fwd ? 0 : (uint64_t)rec_dense * D * sizeof(double);
-  // PathCold (wavelength, dielectric point) is read only by the spectral sampler and glass
-  const bool need_cold = spectral || !ctx->sc.no_pathlen;
-  // a hit's (u, v) array: read by (u, v)-reading textures and, for spheres, the root (A16)
-  const bool need_uv = !ctx->sc.tri_only || ctx->any_uv;
-  // Paths in flight per wavefront pass. Larger = fewer k_trace/k_shade launches and
-  // a smaller share of launch tails.
-  // C3 per frame (round 2, tiered records): 40M slots 349 ms, 100M 334, 160M 326, 250M 320
-  // (fewer passes and pass tails; the first frame, fresh allocations included, is faster
-  // too: 371 ms at 40M, 349 ms at 250M); C5 at 64 spp 120M slots: -6%; C4 100M: -3%.
-  // The state stays within half of the HBM (below).
-  uint64_t slot_cap = 256ull << 20;
-  if (tu.slots) slot_cap = std::max<uint64_t>(1024, tu.slots);
-  const uint64_t per_slot = 2 * (sizeof(RayOD) + sizeof(uint32_t) + (ctx->sc.tri_only ? 0 : sizeof(double)) + sizeof(PathHot) +
-                                 sizeof(uint32_t) + (need_cold ? sizeof(PathCold) : 0) + sizeof(double2) * (need_uv ? 2 : 1) +
-                                 thr_planes * sizeof(double)) +
-                            rec_bytes_slot;
-  // Overflow blocks per slot. Lambert/light scenes: 1 per 16 slots (C3: ~3% of the paths
-  // in flight are deeper than 8). Scenes with glass or the spectral sampler run deep
-  // chains through glass: 1 per 4 slots (C5 at 1 per 16 parked 29% of its
-  // shading items, 574 -> 502 ms per 16-spp frame with no parks at 1 per 4). A frame that
-  // still parks more than 1/64 of its rays doubles the pool for the renderer's next frame.
-  // Metal / PBR scenes without glass stay at 1 per 16: C4's paths (1.85 rays per sample)
-  // park none, and 1 per 4 allocated 56 GB of pool there (a second of a first frame on
-  // boxes whose driver clears memory as it maps it).
-  uint32_t pool_div = (spectral || !ctx->sc.no_pathlen) ? 4u : 16u;
-  pool_div = std::max(1u, pool_div >> std::min(ctx->pool_grow, 4u));
-  if (tu.pool_div) pool_div = tu.pool_div;
-  if (reuse) pool_div = ctx->sizing.pool_div;
-  const uint64_t per_block = (uint64_t)rec_pool * D * sizeof(double) + sizeof(uint32_t);
-  // The wavefront state in the rest of the workspace budget. The overflow pool rounds up
-  // to a power of two per ring, up to twice slots / pool_div blocks: counted at that worst
-  // case (C4 at 256M slots otherwise took 271 GB of the 288). C3 keeps its 256M slots
-  // (135 GB); C5 at 128 spp ran 1.4% faster at 64M slots than at 118M (less state, better
-  // cache and TLB reach in k_shade), so the smaller budget costs the deep-path scenes nothing.
-  const uint64_t samples_bytes = (uint64_t)num_pixels * chunk * SMP_D * sizeof(double);
-  const uint64_t budget = avail / 32 * 15;
-  if (avail > 0)
-    slot_cap = std::min<uint64_t>(slot_cap, std::max<uint64_t>(1024, (budget > samples_bytes ? budget - samples_bytes : 0) /
-                                                                          (per_slot + 2 * per_block / pool_div + 1)));
-  const uint32_t slots = reuse ? ctx->sizing.slots : (uint32_t)std::min<uint64_t>((uint64_t)num_pixels * chunk, slot_cap);
-  uint32_t pool_blocks = 0;
-  if (rec_pool) {  // POOL_SHARDS rings of a power of two each, at least 16 blocks per ring
-    pool_blocks = POOL_SHARDS * 16;
-    while (pool_blocks < slots / pool_div && pool_blocks < (1u << 30)) pool_blocks <<= 1;
+  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b == 0) return 0;
+  return ((uint64_t)free_b + render_buffer_bytes(ctx)) / std::max(1u, ctx->dev_share);
+}
+
+// ... and its buffers. The path samplers: when a render buffer must grow, all are released
+// before any is allocated, so a frame never holds an old buffer next to a new one (the plan
+// counted every one of them as available). The preview samplers stay within the buffers a
+// Colour render of this context may already hold: they only grow. A failed allocation drops
+// the family's cached plan.
+int allocate(izpi_ctx* ctx, const izpi_render_req* req, const RequestShape& rs, const WorkspacePlan& plan, const Tracer& tr,
+             const RenderCall& call) {
+  const auto bufs = ctx_buffers(ctx);
+  const size_t bytes[RENDER_BUFS] = {plan.samples_bytes, plan.recs_bytes, plan.pool_bytes, plan.ring_bytes,
+                                     plan.running_bytes, plan.state_bytes, tr.spill_bytes};
+  int rc = IZPI_OK;
+  if (rs.preview) {
+    if ((rc = session_keeps_sums(ctx, call, ctx->running_cap < plan.running_bytes))) return rc;
+    for (size_t k = 0; k < RENDER_BUFS && !rc; k++) rc = grow(ctx, bufs[k].p, bufs[k].cap, bytes[k]);
+  } else {
+    bool fresh = false;
+    rc = grow_render_buffers(ctx, bufs.data(), bytes, &fresh);
+    if (!rc && (rc = session_keeps_sums(ctx, call, fresh))) return rc;
   }
-  memcpy(ctx->sizing.key, size_key, sizeof(size_key));
-  ctx->sizing.chunk = chunk; ctx->sizing.slots = slots; ctx->sizing.pool_blocks = pool_blocks; ctx->sizing.pool_div = pool_div;
-  ctx->sizing_valid = true;
-  const bool need_time = !ctx->sc.tri_only;  // only sphere tests read the ray time
-  // The render buffers this frame needs. When one of them must grow, all are released
-  // before any is allocated, so a frame never holds an old buffer next to a new one (the
-  // sizing above counted every one of them as available).
-  const double t_sized = host_ms();
-  const auto t_alloc0 = std::chrono::steady_clock::now();
-  RenderBuf need[] = {
-      {(void**)&ctx->d_samples, &ctx->samples_cap, (size_t)num_pixels * chunk * SMP_D * sizeof(double)},
-      {(void**)&ctx->d_recs, &ctx->recs_cap, (size_t)rec_bytes_slot * slots},
-      {(void**)&ctx->d_pool, &ctx->pool_cap, rec_pool ? (size_t)pool_blocks * rec_pool * D * sizeof(double) : 0},
-      {(void**)&ctx->d_ring, &ctx->ring_cap, rec_pool ? (size_t)pool_blocks * sizeof(uint32_t) : 0},
-      {(void**)&ctx->d_running, &ctx->running_cap, (size_t)num_pixels * 3 * sizeof(double)},
-      {(void**)&ctx->d_state, &ctx->state_cap, carve_state(nullptr, slots, need_time, rec_pool != 0, need_cold, need_uv, thr_planes, nullptr)},
-      {(void**)&ctx->d_spill, &ctx->spill_cap, tr.spill_bytes},
-  };
-  bool fresh = false;
-  if ((rc = grow_render_buffers(ctx, need, sizeof(need) / sizeof(need[0]), &fresh))) {
-    ctx->sizing_valid = false;
-    return rc;
+  if (!rc) rc = grow(ctx, (void**)&ctx->d_tiles, &ctx->tiles_cap, rs.tiles.size() * sizeof(uint32_t));
+  if (!rc && !rs.preview) {  // (the preview samplers read no background SPD)
+    if (req->num_bg_spd && (!req->bg_spd_wavelengths || !req->bg_spd_values)) { ctx->err = "num_bg_spd without the SPD arrays"; return IZPI_ERR_INVALID; }
+    rc = grow(ctx, (void**)&ctx->d_bg, &ctx->bg_cap, (2 * (size_t)req->num_bg_spd + 1) * sizeof(double));
   }
-  if ((rc = session_keeps_sums(ctx, sr, fresh))) return rc;
-  if ((rc = grow(ctx, (void**)&ctx->d_tiles, &ctx->tiles_cap, tiles.size() * sizeof(uint32_t)))) return rc;
-  const size_t nbg = req->num_bg_spd;
-  if (nbg && (!req->bg_spd_wavelengths || !req->bg_spd_values)) { ctx->err = "num_bg_spd without the SPD arrays"; return IZPI_ERR_INVALID; }
-  if ((rc = grow(ctx, (void**)&ctx->d_bg, &ctx->bg_cap, (2 * nbg + 1) * sizeof(double)))) return rc;
-  // counter rows: one per wave of the largest grid (run_chunks checks the grids against it)
-  const uint32_t cpart_rows = ctx->num_cus * CPART_BLOCKS_PER_CU * 4u;
-  if ((rc = grow(ctx, (void**)&ctx->d_cpart, &ctx->cpart_cap, (size_t)cpart_rows * CNT_N * sizeof(unsigned long long)))) return rc;
+  if (!rc) rc = grow(ctx, (void**)&ctx->d_cpart, &ctx->cpart_cap, (size_t)cpart_rows(ctx) * CNT_N * sizeof(unsigned long long));
   // deferred unwinding jobs: one queue per k_shade block (run_chunks checks its grid against it)
-  if (!fwd && (rc = grow(ctx, (void**)&ctx->d_finq, &ctx->finq_cap, (size_t)ctx->num_cus * CPART_BLOCKS_PER_CU * FINQ_WORDS * FINQ_CAP * sizeof(unsigned long long)))) return rc;
-  const double alloc_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_alloc0).count();
-  if (ctx->prepare_only) {
-    // izpi_gpu_prepare: the device's first work on the fresh workspace (its first submission
-    // after a large allocation waited ~7 ms, and the kernels' first touch of its pages)
-    // happens here, in the renderer's setup, not in its first frame
-    hipStream_t ps = ctx->stream;
-    HIP_TRY(hipMemsetAsync(ctx->d_state, 0, ctx->state_cap, ps));
-    HIP_TRY(hipMemsetAsync(ctx->d_samples, 0, ctx->samples_cap, ps));
-    if (ctx->d_recs) HIP_TRY(hipMemsetAsync(ctx->d_recs, 0, ctx->recs_cap, ps));
-    if (sr.keep) {  // izpi_gpu_progressive_begin: the session's sums and counters start at zero
-      HIP_TRY(hipMemsetAsync(ctx->d_running, 0, (size_t)num_pixels * 3 * sizeof(double), ps));
-      HIP_TRY(hipMemsetAsync(ctx->d_counters, 0, CNT_N * sizeof(unsigned long long), ps));
-    }
-    HIP_TRY(hipStreamSynchronize(ps));
-    ctx->last = izpi_render_stats{};
-    ctx->last.workspace_bytes = workspace_bytes(ctx);
-    ctx->last.slots = slots; ctx->last.chunk_spp = chunk; ctx->last.alloc_ms = alloc_ms;
-    return IZPI_OK;
-  }
-  if (tu.flags & IZPI_TUNE_PASS_LOG) HIP_TRY(hipEventRecord(ctx->evb[0], ctx->stream));
-  WaveBuf bufs[2];
-  carve_state(ctx->d_state, slots, need_time, rec_pool != 0, need_cold, need_uv, thr_planes, bufs);
+  if (!rc && !rs.preview && !rs.fwd) rc = grow(ctx, (void**)&ctx->d_finq, &ctx->finq_cap, (size_t)ctx->num_cus * CPART_BLOCKS_PER_CU * FINQ_WORDS * FINQ_CAP * sizeof(unsigned long long));
+  if (rc) ctx->plans[rs.preview].valid = false;
+  return rc;
+}
+
+// 3. prepare_only (izpi_gpu_prepare, a session's begin): the device's first work on the fresh
+// workspace (its first submission after a large allocation waited ~7 ms, and the kernels'
+// first touch of its pages) happens here, in the renderer's setup, not in its first frame.
+int touch_workspace(izpi_ctx* ctx, const WorkspacePlan& plan, const RenderCall& call, double alloc_ms) {
   hipStream_t st = ctx->stream;
-  HIP_TRY(hipMemcpyAsync(ctx->d_tiles, tiles.data(), tiles.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(ctx->d_state, 0, plan.state_bytes, st));
+  HIP_TRY(hipMemsetAsync(ctx->d_samples, 0, plan.samples_bytes, st));
+  if (plan.recs_bytes) HIP_TRY(hipMemsetAsync(ctx->d_recs, 0, plan.recs_bytes, st));
+  if (call.range.keep) {  // izpi_gpu_progressive_begin: the session's sums and counters start at zero
+    HIP_TRY(hipMemsetAsync(ctx->d_running, 0, plan.running_bytes, st));
+    HIP_TRY(hipMemsetAsync(ctx->d_counters, 0, CNT_N * sizeof(unsigned long long), st));
+  }
+  HIP_TRY(hipStreamSynchronize(st));
+  ctx->last = izpi_render_stats{};
+  ctx->last.workspace_bytes = workspace_bytes(ctx);
+  ctx->last.slots = plan.slots; ctx->last.chunk_spp = plan.chunk; ctx->last.alloc_ms = alloc_ms;
+  return IZPI_OK;
+}
+
+// 4. Begin frame: the tiles and the background SPD (nbg entries) to the device, the sums and
+// counters zeroed (a session's run on from step to step).
+int begin_frame(izpi_ctx* ctx, const izpi_render_req* req, const RequestShape& rs, const WorkspacePlan& plan, const RenderCall& call,
+                size_t nbg) {
+  hipStream_t st = ctx->stream;
+  HIP_TRY(hipMemcpyAsync(ctx->d_tiles, rs.tiles.data(), rs.tiles.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
   if (nbg) {
     HIP_TRY(hipMemcpyAsync(ctx->d_bg, req->bg_spd_wavelengths, nbg * sizeof(double), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(ctx->d_bg + nbg, req->bg_spd_values, nbg * sizeof(double), hipMemcpyHostToDevice, st));
   }
-  if (!sr.keep) {  // (a session's sums and counters run on from step to step)
-    HIP_TRY(hipMemsetAsync(ctx->d_running, 0, (size_t)num_pixels * 3 * sizeof(double), st));
+  if (!call.range.keep) {
+    HIP_TRY(hipMemsetAsync(ctx->d_running, 0, plan.running_bytes, st));
     HIP_TRY(hipMemsetAsync(ctx->d_counters, 0, CNT_N * sizeof(unsigned long long), st));
   }
-  HIP_TRY(hipMemsetAsync(ctx->d_cpart, 0, (size_t)cpart_rows * CNT_N * sizeof(unsigned long long), st));
+  HIP_TRY(hipMemsetAsync(ctx->d_cpart, 0, (size_t)cpart_rows(ctx) * CNT_N * sizeof(unsigned long long), st));
   HIP_TRY(hipMemsetAsync(ctx->d_misc, 0, 8 * MISC_STRIDE * sizeof(uint32_t), st));
+  return IZPI_OK;
+}
 
+// 5. The kernels' parameters. What every sampler's kernels read of ShadeParams ...
+ShadeParams shade_params(izpi_ctx* ctx, const izpi_render_req* req, const RequestShape& rs, const WorkspacePlan& plan) {
   ShadeParams sp{};
-  sp.width = req->width; sp.height = req->height; sp.max_depth = req->max_depth;
-  sp.tile_w = tw; sp.tile_h = th; sp.num_bg_spd = (uint32_t)nbg; sp.slots = slots;
+  sp.width = req->width; sp.height = req->height; sp.tile_w = rs.tw; sp.tile_h = rs.th; sp.slots = plan.slots;
+  // (the preview samplers ignore the request's; start_path completes a sample of max_depth 0 at once)
+  sp.max_depth = rs.preview ? 1 : req->max_depth;
+  sp.tiles = ctx->d_tiles; sp.seed = req->seed; sp.out = ctx->d_samples;
+  sp.background[0] = req->background[0]; sp.background[1] = req->background[1]; sp.background[2] = req->background[2];
+  sp.counters = ctx->d_counters; sp.cpart = ctx->d_cpart; sp.error = misc(ctx, 1);
+  return sp;
+}
+// ... and what the path samplers' read besides: the background SPD, the records and their
+// overflow pool, the scene's table sizes.
+void path_shade_params(izpi_ctx* ctx, const izpi_render_req* req, const DevScene& sc, const RequestShape& rs,
+                       const WorkspacePlan& plan, size_t nbg, ShadeParams& sp) {
+  sp.num_bg_spd = (uint32_t)nbg;
   sp.bg_sorted = nbg >= 2;
   for (size_t i = 1; i < nbg; i++)
     if (!(req->bg_spd_wavelengths[i - 1] <= req->bg_spd_wavelengths[i])) sp.bg_sorted = 0;
-  sp.tiles = ctx->d_tiles; sp.bg_wl = ctx->d_bg; sp.bg_val = ctx->d_bg + nbg;
-  sp.background[0] = req->background[0]; sp.background[1] = req->background[1]; sp.background[2] = req->background[2];
-  sp.rec_dense = rec_dense; sp.rec_pool = rec_pool;
-  sp.pool_shift = 0;
-  while (pool_blocks && (POOL_SHARDS << sp.pool_shift) < pool_blocks) sp.pool_shift++;
-  sp.seed = req->seed; sp.out = ctx->d_samples; sp.recs = fwd ? nullptr : ctx->d_recs; sp.mat_const = sc.mat_const; sp.head = misc(ctx, 0);
+  sp.bg_wl = ctx->d_bg; sp.bg_val = ctx->d_bg + nbg;
+  sp.rec_dense = plan.rec_dense; sp.rec_pool = plan.rec_pool; sp.pool_shift = plan.pool_shift;
+  sp.recs = rs.fwd ? nullptr : ctx->d_recs; sp.mat_const = sc.mat_const; sp.head = misc(ctx, 0);
   sp.num_mc = ctx->num_materials; sp.num_tex = ctx->num_textures; sp.num_spd = ctx->num_spd;
+  sp.pool = plan.rec_pool ? ctx->d_pool : nullptr; sp.pool_ring = plan.rec_pool ? ctx->d_ring : nullptr;
+  sp.pool_ctr = plan.rec_pool ? ctx->d_pool_ctr : nullptr;
+  sp.finq = ctx->d_finq;
+}
+// Which of the scene's tables this render's k_shade / k_tail blocks copy into LDS
+// (sp.staged, sp.prims_staged), and the LDS arena that takes (sc.lds_bytes).
+void stage_tables(const izpi_ctx* ctx, const izpi_render_req* req, const izpi_render_tuning& tu, const RequestShape& rs,
+                  const WorkspacePlan& plan, size_t nbg, DevScene& sc, ShadeParams& sp) {
   sp.staged = ctx->num_materials <= MC_LDS && ctx->num_materials <= MAT_LDS && sc.num_lights <= LT_LDS &&
               ctx->num_textures <= TEX_LDS && ctx->num_spd <= SPD_LDS && nbg <= BG_LDS;
-  sp.prims_staged = sc.num_prims <= PR_LDS && !(tuning_of(req).flags & IZPI_TUNE_NO_PRIM_LDS);
+  sp.prims_staged = sc.num_prims <= PR_LDS && !(tu.flags & IZPI_TUNE_NO_PRIM_LDS);
   if (sp.staged && (req->sampler == IZPI_SAMPLER_SPECTRAL || ctx->num_spd)) sp.staged = 2;  // + the Spectral tables
   // A forward Colour render of a Lambert / light scene (C1, C2) that could run k_shade's staged
   // form but for its primitives in LDS (the output stage lies behind the Colour tables, where
   // they would) leaves them in global memory: its hits read their 32-B GShade only, and C2's
   // shading at 256 spp measured 35.0-35.3 ms with the primitives in LDS, 34.3-34.4 without and
   // 30.3-30.4 without them in the staged form (run_chunks; profiles/r7b/ab_stage_c2.jsonl).
-  if (fwd && req->sampler == IZPI_SAMPLER_COLOUR && ctx->matset == 0 && sp.staged == 1 && !rec_pool && !need_time && !need_cold &&
-      !(tuning_of(req).flags & IZPI_TUNE_NO_SHADE_STAGE))
+  if (rs.fwd && req->sampler == IZPI_SAMPLER_COLOUR && ctx->matset == 0 && sp.staged == 1 && !plan.rec_pool && !plan.time &&
+      !plan.cold && !(tu.flags & IZPI_TUNE_NO_SHADE_STAGE))
     sp.prims_staged = 0;
   // k_shade / k_tail's LDS arena: the prefix of lds_off's layout that this render stages
   sc.lds_bytes = sp.prims_staged ? lds_off::END : sp.staged == 2 ? lds_off::SPECTRAL_END : sp.staged ? lds_off::COLOUR_END : 0;
   if (tu.flags & IZPI_TUNE_PASS_LOG)  // diagnostics: which tables this render's k_shade / k_tail blocks copy into LDS
     fprintf(stderr, "IZPI_SHADE_TABLES tables=%u prims=%u lds_bytes=%u\n", sp.staged, sp.prims_staged, sc.lds_bytes);
-  sp.pool = rec_pool ? ctx->d_pool : nullptr; sp.pool_ring = rec_pool ? ctx->d_ring : nullptr;
-  sp.pool_ctr = rec_pool ? ctx->d_pool_ctr : nullptr;
-  sp.counters = ctx->d_counters; sp.cpart = ctx->d_cpart; sp.error = misc(ctx, 1);
-  sp.finq = ctx->d_finq;
+}
+WaveParams wave_params(izpi_ctx* ctx, const WorkspacePlan& plan, const ShadeParams& sp) {
   WaveParams wp{};
-  wp.in = bufs[0]; wp.out = bufs[1]; wp.trace_next = misc(ctx, 2); wp.slots = slots;
+  wp.in = bind_side(ctx->d_state, plan, plan.side[0]); wp.out = bind_side(ctx->d_state, plan, plan.side[1]);
+  wp.trace_next = misc(ctx, 2); wp.slots = plan.slots;
   // kind words other than plain main rays: path-length rays, parked entries
   wp.read_kind = !ctx->sc.no_pathlen ? 1u : 0u;  // parked entries: wp.in_park, per pass
-  wp.hit_uv = need_uv ? 1u : 0u;
+  wp.hit_uv = plan.uv ? 1u : 0u;
   wp.pool_ctr = sp.pool_ctr;
   wp.cpart = ctx->d_cpart;
+  return wp;
+}
+PreviewParams preview_params(izpi_ctx* ctx, const izpi_render_req* req, const WorkspacePlan& plan) {
+  PreviewParams pp{};
+  pp.buf = bind_side(ctx->d_state, plan, plan.side[0]);
+  pp.tminmax = plan.tminmax ? (double2*)(ctx->d_state + plan.side[0].tminmax) : nullptr;
+  pp.slots = plan.slots;
+  pp.verts = ctx->d_triverts;
+  if (req->abi_version >= 4)  // (a request of ABI 3 ends before `ink`: black)
+    for (int k = 0; k < 3; k++) pp.ink[k] = req->ink[k];
+  return pp;
+}
+AccumParams accum_params(izpi_ctx* ctx, const izpi_render_req* req, const RequestShape& rs, double* out_dev) {
   AccumParams ap{};
-  ap.num_pixels = num_pixels; ap.spp = req->spp; ap.width = req->width; ap.height = req->height;
-  ap.tile_w = tw; ap.tile_h = th; ap.sampler = req->sampler; ap.out_layout = req->out_layout;
+  ap.num_pixels = rs.num_pixels; ap.spp = req->spp; ap.width = req->width; ap.height = req->height;
+  ap.tile_w = rs.tw; ap.tile_h = rs.th; ap.out_layout = req->out_layout;
+  ap.sampler = rs.preview ? (uint32_t)IZPI_SAMPLER_COLOUR : req->sampler;  // (the preview samplers: col / numSamples, rgb.go:38)
   ap.tiles = ctx->d_tiles; ap.samples = ctx->d_samples; ap.running = ctx->d_running; ap.out = out_dev;
+  return ap;
+}
 
-  float trace_ms = 0, shade_ms = 0, tail_ms = 0;
+// 6. The device's error word (k_trace2 can set bit 1 alone; k_shade and k_tail the others).
+int guard_status(izpi_ctx* ctx, uint32_t guard) {
+  if (!guard) return IZPI_OK;
+  ctx->err = guard & 1u   ? "device guard: traversal stack overflow"
+             : guard & 2u ? "device guard: unknown material kind"
+                            : "device guard: no overflow record block in k_tail";
+  return IZPI_ERR_DEVICE;
+}
+
+// One render on one context, or (call.prepare_only) the allocation of its workspace: the
+// steps above in turn, for every sampler.
+int render_body(izpi_ctx* ctx, const izpi_render_req* req, const RenderCall& call, double* out_dev) {
+  const auto t_body0 = std::chrono::steady_clock::now();
+  auto host_ms = [&t_body0]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_body0).count(); };
+  RequestShape rs;
+  int rc = check_request(ctx, req, &rs);
+  if (rc) return rc;
+  const SampleRange& sr = call.range;
+  const uint32_t num_pixels = rs.num_pixels;
+  if (sr.keep) {
+    izpi_ctx::Session& ss = ctx->session;
+    ss.run_tiles = rs.tiles; ss.tile_w = rs.tw; ss.tile_h = rs.th; ss.num_pixels = num_pixels;
+  }
+  const izpi_render_tuning& tu = tuning_of(req);
+  const bool pass_log = (tu.flags & IZPI_TUNE_PASS_LOG) != 0;
+  // this render's view of the scene: the traversal shortcuts the tuning switches off
+  DevScene sc = ctx->sc;
+  if (tu.flags & IZPI_TUNE_NO_LEAF_SHORTCUT) sc.leaf_shortcut = 0;
+  if (tu.flags & IZPI_TUNE_SCALAR_SLAB) sc.nan_free_bounds = 0;
+  Tracer tr;
+  const double t_tiles = host_ms();
+  if ((rc = make_tracer(ctx, tu, !ctx->sc.tri_only || ctx->any_uv, &tr))) return rc;
+  if (pass_log)  // diagnostics: the k_trace2 instance this render runs
+    fprintf(stderr, "IZPI_TRACE_INSTANCE dist=%d tri=%d lds_bvh=%d ray_lds=%d q=%d\n", (int)tr.p2, (int)tr.tri, (int)tr.lds_bvh,
+            (int)tr.ray_lds, (int)tr.qnodes);
+  const double t_tracer = host_ms();
+  // Plan: the family's cached plan when the request has its shape, else from the free memory.
+  PlanCache& cache = ctx->plans[rs.preview];
+  PlanInput in = plan_input(ctx, req, rs, tu, call.size_spp);
+  const bool reuse = cache.find(in) != nullptr;
+  if (!reuse) in.avail = available_bytes(ctx);
+  const double t_meminfo = host_ms();
+  if (!reuse) cache.store(in, plan_workspace(in));
+  const WorkspacePlan& plan = cache.plan;
+  const double t_sized = host_ms();
+  const auto t_alloc0 = std::chrono::steady_clock::now();
+  if ((rc = allocate(ctx, req, rs, plan, tr, call))) return rc;
+  const double alloc_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_alloc0).count();
+  if (call.prepare_only) return touch_workspace(ctx, plan, call, alloc_ms);
+  hipStream_t st = ctx->stream;
+  if (pass_log) HIP_TRY(hipEventRecord(ctx->evb[0], st));
+  const size_t nbg = rs.preview ? 0 : req->num_bg_spd;  // (the preview samplers read no background SPD)
+  if ((rc = begin_frame(ctx, req, rs, plan, call, nbg))) return rc;
+  ShadeParams sp = shade_params(ctx, req, rs, plan);
+  AccumParams ap = accum_params(ctx, req, rs, out_dev);
+  if (!rs.preview) {
+    path_shade_params(ctx, req, sc, rs, plan, nbg, sp);
+    stage_tables(ctx, req, tu, rs, plan, nbg, sc, sp);
+  }
+
+  float trace_ms = 0, shade_ms = 0, tail_ms = 0, total_ms = 0;
   uint32_t launches = 0;
   const double t_launch = host_ms();
   HIP_TRY(hipEventRecord(ctx->ev0, st));
-  if (tu.flags & IZPI_TUNE_PASS_LOG) {  // diagnostics: the GPU time of the setup copies before ev0
+  if (pass_log) {  // diagnostics: the GPU time of the setup copies before ev0
     HIP_TRY(hipEventSynchronize(ctx->ev0));
     float prep = 0;
     HIP_TRY(hipEventElapsedTime(&prep, ctx->evb[0], ctx->ev0));
     fprintf(stderr, "IZPI_T ev0_synced %.3f prep_gpu_ms %.3f body_start %.3f\n", diag_clock_ms(), prep,
             diag_clock_ms() - host_ms());
   }
-#define IZPI_RUN(S, F) run_sampler<S, F>(ctx, req, sc, tr, sp, wp, ap, num_pixels, chunk, pool_blocks, compact, sr, &trace_ms, \
-                                        &shade_ms, &tail_ms, &launches)
-  if (req->sampler == IZPI_SAMPLER_COLOUR) rc = fwd ? IZPI_RUN(IZPI_SAMPLER_COLOUR, true) : IZPI_RUN(IZPI_SAMPLER_COLOUR, false);
-  else rc = fwd ? IZPI_RUN(IZPI_SAMPLER_SPECTRAL, true) : IZPI_RUN(IZPI_SAMPLER_SPECTRAL, false);
+  if (rs.preview) {
+    const PreviewParams pp = preview_params(ctx, req, plan);
+    rc = run_preview(ctx, req, sc, tr, sp, pp, ap, num_pixels, plan.chunk, sr, &trace_ms, &shade_ms, &launches);
+  } else {
+    WaveParams wp = wave_params(ctx, plan, sp);
+#define IZPI_RUN(S, F) run_sampler<S, F>(ctx, req, sc, tr, sp, wp, ap, num_pixels, plan.chunk, plan.pool_blocks, plan.compact, sr, \
+                                        &trace_ms, &shade_ms, &tail_ms, &launches)
+    if (req->sampler == IZPI_SAMPLER_COLOUR) rc = rs.fwd ? IZPI_RUN(IZPI_SAMPLER_COLOUR, true) : IZPI_RUN(IZPI_SAMPLER_COLOUR, false);
+    else rc = rs.fwd ? IZPI_RUN(IZPI_SAMPLER_SPECTRAL, true) : IZPI_RUN(IZPI_SAMPLER_SPECTRAL, false);
 #undef IZPI_RUN
+  }
   if (rc) return rc;
-  hipLaunchKernelGGL(k_cpart_reduce, dim3(CNT_N), dim3(256), 0, st, ctx->d_cpart, cpart_rows, ctx->d_counters);
+  // End frame: the per-wave counter rows summed, the request's post-processing, then the
+  // counters and the error word back to the host.
+  hipLaunchKernelGGL(k_cpart_reduce, dim3(CNT_N), dim3(256), 0, st, ctx->d_cpart, cpart_rows(ctx), ctx->d_counters);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(ctx->ev1, st));
   if (!sr.keep && (rc = apply_post(ctx, req, out_dev))) return rc;
   const double t_issued = host_ms();
   HIP_TRY(hipEventSynchronize(ctx->ev1));
-  if (tu.flags & IZPI_TUNE_PASS_LOG)  // diagnostics: where the call's host time goes
+  if (pass_log)  // diagnostics: where the call's host time goes
     fprintf(stderr, "IZPI_HOST tiles %.3f tracer %.3f meminfo %.3f sized %.3f allocated %.3f launched %.3f issued %.3f done %.3f ms\n",
             t_tiles, t_tracer, t_meminfo, t_sized, t_sized + alloc_ms, t_launch, t_issued, host_ms());
-  float total_ms = 0;
   HIP_TRY(hipEventElapsedTime(&total_ms, ctx->ev0, ctx->ev1));
   unsigned long long cnt[CNT_N];
-  uint32_t misc_w[MISC_STRIDE + 1];
+  uint32_t guard = 0;
   HIP_TRY(hipMemcpy(cnt, ctx->d_counters, sizeof(cnt), hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(misc_w, misc(ctx, 0), sizeof(misc_w), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&guard, misc(ctx, 1), sizeof(guard), hipMemcpyDeviceToHost));
+  // (the preview samplers run no light tests, no k_tail and park nothing: those counters stay zero)
   izpi_render_stats& s = ctx->last;
   memset(&s, 0, sizeof(s));
   s.rays = cnt[CNT_RAYS]; s.node_visits = cnt[CNT_NODES]; s.tri_tests = cnt[CNT_TRI]; s.sph_tests = cnt[CNT_SPH];
@@ -857,10 +744,10 @@ int render_body(izpi_ctx* ctx, const izpi_render_req* req, double* out_dev) {
   s.parks = cnt[CNT_PARK];
   s.workspace_bytes = workspace_bytes(ctx);
   s.scene_bytes = ctx->scene_bytes;
-  s.slots = slots; s.rec_dense = fwd ? 0 : rec_dense; s.pool_blocks = pool_blocks; s.chunk_spp = chunk;
+  s.slots = plan.slots; s.rec_dense = rs.fwd ? 0 : plan.rec_dense; s.pool_blocks = plan.pool_blocks; s.chunk_spp = plan.chunk;
   s.alloc_ms = alloc_ms;
   // (not within a session: a larger pool would re-allocate the workspace, the sums with it)
-  if (!sr.keep && rec_pool && s.parks * 64 > s.rays && pool_blocks < slots) ctx->pool_grow++;
+  if (!sr.keep && plan.rec_pool && s.parks * 64 > s.rays && plan.pool_blocks < plan.slots) ctx->pool_grow++;
 #ifdef IZPI_SHADE_CLOCKS
   fprintf(stderr, "IZPI_SHADE_CLOCKS item %llu refill %llu push %llu mat %llu finish %llu mix %llu lpdf %llu entry %llu tex %llu "
           "res_barrier1 %llu res_atomics %llu res_barrier2 %llu (wave cycles; res_atomics: thread 0 only)\n",
@@ -875,14 +762,18 @@ int render_body(izpi_ctx* ctx, const izpi_render_req* req, double* out_dev) {
   fprintf(stderr, "IZPI_TRACE_CLOCKS refill %llu node %llu prim %llu advance %llu (wave cycles)\n", cnt[CNT_CLK_REFILL],
           cnt[CNT_CLK_NODE], cnt[CNT_CLK_PRIM], cnt[CNT_CLK_ADV]);
 #endif
-  const uint32_t guard = misc_w[MISC_STRIDE];  // the error word
-  if (guard) {
-    ctx->err = guard & 1u   ? "device guard: traversal stack overflow"
-               : guard & 2u ? "device guard: unknown material kind"
-                              : "device guard: no overflow record block in k_tail";
-    return IZPI_ERR_DEVICE;
-  }
-  return IZPI_OK;
+  return guard_status(ctx, guard);
+}
+
+// One render on one context. The progress counters (izpi_gpu_progress) start at 0/0 before
+// any check and read done == total on every return, failed calls included.
+int render_impl(izpi_ctx* ctx, const izpi_render_req* req, const RenderCall& call, double* out_dev) {
+  if (session_open(ctx)) return IZPI_ERR_INVALID;  // (before the progress counters: they are the session's)
+  ctx->prog_done.store(0, std::memory_order_relaxed);
+  ctx->prog_total.store(0, std::memory_order_relaxed);
+  const int rc = render_body(ctx, req, call, out_dev);
+  ctx->prog_done.store(ctx->prog_total.load(std::memory_order_relaxed), std::memory_order_relaxed);
+  return rc;
 }
 
 // ------------------------------------------------------------------ multi-GPU
@@ -944,10 +835,7 @@ int render_share(izpi_ctx* ctx, const izpi_render_req* req, const Shares& sh, ui
   q.tiles = mine.data();
   q.out_layout = IZPI_OUT_PACKED;
   q.post = IZPI_POST_NONE;
-  ctx->prepare_only = prepare_only;
-  const int rc = render_impl(ctx, &q, prepare_only ? nullptr : ctx->d_share);
-  ctx->prepare_only = false;
-  return rc;
+  return render_impl(ctx, &q, one_shot(&q, prepare_only), prepare_only ? nullptr : ctx->d_share);
 }
 
 // Root: scatter every share's packed tiles from d_gather into the canvas (row H - y,
@@ -1001,7 +889,7 @@ void session_drop(izpi_ctx* ctx) {
   ctx->prog_total.store(0, std::memory_order_relaxed);
 }
 
-// begin: render_body's own checks, sizing and allocation for a request of step_spp samples
+// begin: render_body's own checks, plan and allocation for a request of step_spp samples
 // (its prepare_only form, which for a session also zeroes the sums and the counters).
 int session_begin(izpi_ctx* ctx, const izpi_render_req* req, uint32_t step_spp) {
   if (ctx->session.open) { ctx->err = "a progressive session is already open"; return IZPI_ERR_INVALID; }
@@ -1010,10 +898,7 @@ int session_begin(izpi_ctx* ctx, const izpi_render_req* req, uint32_t step_spp) 
   int rc = session_copy_request(ss, req, ctx->err);
   if (!rc) {
     ss.step_spp = std::min(step_spp, std::max(1u, ss.req.spp));
-    const SampleRange sr{0, 0, true};
-    ctx->range = &sr; ctx->size_spp = ss.step_spp; ctx->prepare_only = true;
-    rc = render_body(ctx, &ss.req, nullptr);
-    ctx->range = nullptr; ctx->prepare_only = false;
+    rc = render_body(ctx, &ss.req, RenderCall{SampleRange{0, 0, true}, ss.step_spp, true}, nullptr);
   }
   if (rc) {
     const std::string why = ctx->err;
@@ -1042,10 +927,7 @@ int session_step(izpi_ctx* ctx, uint32_t spp, izpi_render_stats* stats) {
   izpi_ctx::Session& ss = ctx->session;
   const uint32_t n = std::min(spp ? spp : ss.step_spp, ss.req.spp - ss.done);
   if (n) {
-    const SampleRange sr{ss.done, ss.done + n, true};
-    ctx->range = &sr; ctx->size_spp = ss.step_spp;
-    rc = render_body(ctx, &ss.req, nullptr);
-    ctx->range = nullptr;
+    rc = render_body(ctx, &ss.req, RenderCall{SampleRange{ss.done, ss.done + n, true}, ss.step_spp, false}, nullptr);
     if (rc) {  // a chunk may or may not be in the sums
       ss.broken = true;
       return rc;
@@ -1201,8 +1083,7 @@ int upload_packed(izpi_ctx* ctx, const izpi_scene_desc* d, const PackedScene& ps
   ctx->num_materials = d->num_materials;
   ctx->num_spd = d->num_spd;
   ctx->have_scene = true;
-  ctx->sizing_valid = false;  // per-slot sizes depend on the scene
-  ctx->pv_sizing_valid = false;
+  ctx->plans[0].valid = ctx->plans[1].valid = false;  // per-slot sizes depend on the scene
   // Load the code of the kernels this scene's renders run now, as part of the scene setup
   // (izpi's Render timer starts after it, renderer.go:170): a first occupancy query loads a
   // kernel's code object, 14 ms of a fresh renderer's first frame otherwise.
@@ -1254,11 +1135,9 @@ int izpi_gpu_close(izpi_ctx* ctx) {
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   if (ctx->comm) (void)ncclCommDestroy(ctx->comm);
   free_scene(ctx);
-  void* bufs[] = {ctx->d_samples, ctx->d_recs, ctx->d_pool, ctx->d_ring, ctx->d_pool_ctr, ctx->d_running, ctx->d_out,
-                  ctx->d_tiles, ctx->d_utiles, ctx->d_bg, ctx->d_misc, ctx->d_counters, ctx->d_state,
-                  ctx->d_spill, ctx->d_post, ctx->d_share,
-                  ctx->d_gather, ctx->d_status, ctx->d_cpart, ctx->d_finq};
-  for (void* p : bufs) if (p) (void)hipFree(p);
+  for (const CtxBuf& b : ctx_buffers(ctx)) if (*b.p) (void)hipFree(*b.p);
+  void* fixed[] = {ctx->d_pool_ctr, ctx->d_misc, ctx->d_counters, ctx->d_status};
+  for (void* p : fixed) if (p) (void)hipFree(p);
   if (ctx->h_count) (void)hipHostFree(ctx->h_count);
   if (ctx->stall_host) (void)hipHostFree(ctx->stall_host);
   for (int i = 0; i < 3 * IZPI_PASS_BATCH; i++) if (ctx->evb[i]) (void)hipEventDestroy(ctx->evb[i]);
@@ -1296,7 +1175,7 @@ int izpi_gpu_render_device(izpi_ctx* ctx, const izpi_render_req* req, double* ou
   if (!ctx) return IZPI_ERR_INVALID;
   if (!out_dev) { ctx->err = "null output"; return IZPI_ERR_INVALID; }
   HIP_TRY(hipSetDevice(ctx->device));
-  int rc = render_impl(ctx, req, out_dev);
+  int rc = render_impl(ctx, req, one_shot(req), out_dev);
   if (stats) *stats = ctx->last;
   return rc;
 }
@@ -1311,7 +1190,7 @@ int izpi_gpu_render(izpi_ctx* ctx, const izpi_render_req* req, double* out_host,
   if (rc) return rc;
   // start from the caller's buffer so untouched pixels keep their values
   HIP_TRY(hipMemcpyAsync(ctx->d_out, out_host, bytes, hipMemcpyHostToDevice, ctx->stream));
-  rc = render_impl(ctx, req, ctx->d_out);
+  rc = render_impl(ctx, req, one_shot(req), ctx->d_out);
   if (stats) *stats = ctx->last;
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(out_host, ctx->d_out, bytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -1330,10 +1209,7 @@ int izpi_gpu_prepare(izpi_ctx* ctx, const izpi_render_req* req) {
     if (!rc) rc = share_buffers(ctx, sh, ctx->comm_rank == 0);
     return rc ? rc : render_share(ctx, req, sh, ctx->comm_rank, true);
   }
-  ctx->prepare_only = true;
-  const int rc = render_impl(ctx, req, nullptr);
-  ctx->prepare_only = false;
-  return rc;
+  return render_impl(ctx, req, one_shot(req, true), nullptr);
 }
 
 int izpi_gpu_progressive_begin(izpi_ctx* ctx, const izpi_render_req* req, uint32_t step_spp) {
@@ -2025,14 +1901,11 @@ int izpi_gpu_debug_realloc(izpi_ctx* ctx, uint32_t mask) {
   if (session_open(ctx)) return IZPI_ERR_INVALID;  // (the fresh buffers are not copies: the sums would be lost)
   HIP_TRY(hipSetDevice(ctx->device));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
-  struct { void** p; size_t cap; } bufs[] = {{(void**)&ctx->d_samples, ctx->samples_cap}, {(void**)&ctx->d_recs, ctx->recs_cap},
-                                             {(void**)&ctx->d_pool, ctx->pool_cap}, {(void**)&ctx->d_ring, ctx->ring_cap},
-                                             {(void**)&ctx->d_running, ctx->running_cap}, {(void**)&ctx->d_state, ctx->state_cap},
-                                             {(void**)&ctx->d_spill, ctx->spill_cap}};
-  for (uint32_t k = 0; k < sizeof(bufs) / sizeof(bufs[0]); k++) {
-    if (!(mask >> k & 1u) || !*bufs[k].p || !bufs[k].cap) continue;
+  const auto bufs = ctx_buffers(ctx);
+  for (size_t k = 0; k < RENDER_BUFS; k++) {
+    if (!(mask >> k & 1u) || !*bufs[k].p || !*bufs[k].cap) continue;
     void* fresh = nullptr;  // allocated while the old buffer is still held: other pages
-    HIP_TRY(hipMalloc(&fresh, bufs[k].cap));
+    HIP_TRY(hipMalloc(&fresh, *bufs[k].cap));
     HIP_TRY(hipFree(*bufs[k].p));
     *bufs[k].p = fresh;
   }

@@ -2,7 +2,8 @@
 //   trace.hip     k_trace2 (BVH4.Hit) and its instance selection;
 //   shade.hip     k_start / k_shade / k_tail / k_accumulate and the wavefront pass loop;
 //   preview.hip   k_preview_start / k_preview: the Normal, Albedo and WireFrame samplers;
-//   izpi_gpu.hip  the C ABI, the context, scene upload, workspace sizing, multi-GPU.
+//   izpi_gpu.hip  the C ABI, the context, scene upload, the render call, multi-GPU
+//                 (render_plan.cpp: its workspace plan, plain C++).
 // Device helpers (textures, spectra, the wavefront state, hit records, lights, materials,
 // the shading records) and the host context live here. Not part of the ABI.
 #pragma once
@@ -39,6 +40,7 @@
 #include "../../include/izpi_gpu_debug.h"
 #include "izpi_dev.h"
 #include "izpi_req.h"
+#include "render_plan.h"
 #include "cie_tables.h"
 
 using namespace izd;
@@ -143,7 +145,7 @@ IZPI_DEV T tld(const T* p) {
 constexpr uint32_t MAT_LDS = 64, TEX_LDS = 64, SPD_LDS = 384, BG_LDS = 128, MT_LDS = 64, LT_LDS = 64, PR_LDS = 64;
 // The staged tables live at fixed offsets of the block's dynamic LDS arena, ordered so that
 // what a render stages is a prefix of it: the Colour tables, then the Spectral ones, then
-// the primitives. render_body sizes the arena to that prefix (lds_arena_bytes), so a render
+// the primitives. stage_tables (izpi_gpu.hip) sizes the arena to that prefix, so a render
 // that stages little leaves k_tail (whose traversal stacks are LDS too) more blocks per CU.
 // The offsets are compile-time: per-render offsets cost k_shade registers (the Spectral
 // instances spilled 8 more VGPRs, C5's shading +2.5%; profiles/r5a/ab_arena_c5.jsonl).
@@ -1456,6 +1458,16 @@ struct ResolveParams {
 };
 void launch_resolve(hipStream_t st, const ResolveParams& rp);
 // ================================================================ host side
+// The record sizes the workspace planner counts with (render_plan.h), against the real types.
+static_assert(sizeof(RayOD) == izpi_internal::plan_size::RAY && sizeof(PathHot) == izpi_internal::plan_size::PATH_HOT &&
+                  sizeof(PathCold) == izpi_internal::plan_size::PATH_COLD && sizeof(double2) == izpi_internal::plan_size::HIT,
+              "render_plan.h: entry records");
+static_assert(SMP_D == izpi_internal::plan_size::SMP_D && POOL_SHARDS == izpi_internal::plan_size::POOL_SHARDS,
+              "render_plan.h: per-sample results, pool rings");
+static_assert(RecLayout<IZPI_SAMPLER_COLOUR, MATSET_FULL>::D == izpi_internal::plan_size::REC_COLOUR &&
+                  RecLayout<IZPI_SAMPLER_COLOUR, MATSET_CONST>::D == izpi_internal::plan_size::REC_COMPACT &&
+                  RecLayout<IZPI_SAMPLER_SPECTRAL, MATSET_FULL>::D == izpi_internal::plan_size::REC_SPECTRAL,
+              "render_plan.h: record strides");
 // Scratch device buffers of one ABI call, freed when it returns (on every path).
 struct DevBufs {
   std::vector<void*> p;
@@ -1482,16 +1494,10 @@ struct izpi_ctx {
   uint32_t num_textures = 0;     // of the uploaded scene (izpi_gpu_gomath texture lookups)
   uint32_t num_materials = 0;    // of the uploaded scene
   uint32_t num_spd = 0;          // tabulated SPD entries of the uploaded scene
-  // The workspace sizing of the last render and what it was decided for (render_impl): a
-  // request of the same shape reuses it, so frames of one renderer never re-size (sizing
-  // from the free HBM of each frame made C4 reallocate its 148 GB every frame, 2 s each).
-  struct Sizing {
-    uint64_t key[8];
-    uint32_t chunk, slots, pool_blocks, pool_div;
-  } sizing{};
-  bool sizing_valid = false;
-  Sizing pv_sizing{};            // the same for the preview samplers' workspace (preview_body)
-  bool pv_sizing_valid = false;
+  // The workspace plan of the last render per sampler family, [0] Colour / Spectral, [1] the
+  // preview samplers (render_plan.h): a Colour frame and a preview frame alternating on one
+  // context do not evict each other's.
+  izpi_internal::PlanCache plans[2];
   const GTriVerts* d_triverts = nullptr;  // [num_prims], leaf order: the triangles' v1, v2 (WireFrame's edge test); a scene allocation
   DevScene sc{};
   uint32_t stack_needed = 0;
@@ -1513,7 +1519,7 @@ struct izpi_ctx {
   unsigned long long* d_counters = nullptr;
   unsigned long long* d_cpart = nullptr; size_t cpart_cap = 0;  // per-wave counter rows of a render (count_add)
   unsigned long long* d_finq = nullptr; size_t finq_cap = 0;  // k_shade blocks' deferred unwinding jobs (fin_flush)
-  char* d_state = nullptr; size_t state_cap = 0;      // the two WaveBufs (carve_state)
+  char* d_state = nullptr; size_t state_cap = 0;      // the sides of the wavefront state (WorkspacePlan::side)
   int32_t* d_spill = nullptr; size_t spill_cap = 0;  // traversal-stack spill area of k_trace2
   double* d_post = nullptr; size_t post_cap = 0;      // spectral post-processing output
   double* d_share = nullptr; size_t share_cap = 0;    // multi-GPU: this device's packed tiles
@@ -1529,7 +1535,6 @@ struct izpi_ctx {
   uint32_t comm_rank = 0, comm_size = 1;
   int32_t* d_status = nullptr;   // agreement word of izpi_gpu_render_rank ([0] in, [1] max over ranks)
   int fault_inject = 0;          // izpi_gpu_debug_fault: 1 fail before rendering, 2 fail the render
-  bool prepare_only = false;     // izpi_gpu_prepare: render_body sizes and allocates, then returns
   izpi_render_stats last{};
   bool mat_ok_rgb = false, mat_ok_spectral = false;
   bool basic_materials = false;  // only Lambertian + DiffuseLight: use the MATSET_BASIC shader
@@ -1543,8 +1548,7 @@ struct izpi_ctx {
   std::atomic<uint64_t> prog_done{0}, prog_total{0};
   // The progressive session of this context (izpi_gpu_progressive_*), when open: the
   // library's copy of the request (req.spp is the cap N; its arrays are the vectors here),
-  // the samples done, and the statistics summed over the steps. `range` is what render_body
-  // renders while the session drives it (null for a one-shot render).
+  // the samples done, and the statistics summed over the steps.
   struct Session {
     bool open = false;
     bool broken = false;  // a step failed: the sums are not those of `done` samples
@@ -1558,8 +1562,6 @@ struct izpi_ctx {
     uint32_t tile_w = 0, tile_h = 0, num_pixels = 0;
     izpi_render_stats cum{};
   } session;
-  const SampleRange* range = nullptr;
-  uint32_t size_spp = 0;  // with `range`: the samples the workspace is sized for (step_spp)
 };
 
 // The words of d_misc lie MISC_STRIDE words (256 B) apart: the unit head and the queue
