@@ -410,7 +410,7 @@ int session_keeps_sums(izpi_ctx* ctx, const RenderCall& call, bool moved) {
   return IZPI_ERR_INVALID;
 }
 
-// counter rows: one per wave of the largest grid (run_chunks and run_preview check the grids against it)
+// counter rows: one per wave of the largest grid (run_wavefront and run_preview check the grids against it)
 uint32_t cpart_rows(const izpi_ctx* ctx) { return ctx->num_cus * CPART_BLOCKS_PER_CU * 4u; }
 
 // ---- render_body's steps, shared by the path samplers and the preview samplers
@@ -511,7 +511,7 @@ int allocate(izpi_ctx* ctx, const izpi_render_req* req, const RequestShape& rs, 
     rc = grow(ctx, (void**)&ctx->d_bg, &ctx->bg_cap, (2 * (size_t)req->num_bg_spd + 1) * sizeof(double));
   }
   if (!rc) rc = grow(ctx, (void**)&ctx->d_cpart, &ctx->cpart_cap, (size_t)cpart_rows(ctx) * CNT_N * sizeof(unsigned long long));
-  // deferred unwinding jobs: one queue per k_shade block (run_chunks checks its grid against it)
+  // deferred unwinding jobs: one queue per k_shade block (run_wavefront checks its grid against it)
   if (!rc && !rs.preview && !rs.fwd) rc = grow(ctx, (void**)&ctx->d_finq, &ctx->finq_cap, (size_t)ctx->num_cus * CPART_BLOCKS_PER_CU * FINQ_WORDS * FINQ_CAP * sizeof(unsigned long long));
   if (rc) ctx->plans[rs.preview].valid = false;
   return rc;
@@ -594,7 +594,7 @@ void stage_tables(const izpi_ctx* ctx, const izpi_render_req* req, const izpi_re
   // form but for its primitives in LDS (the output stage lies behind the Colour tables, where
   // they would) leaves them in global memory: its hits read their 32-B GShade only, and C2's
   // shading at 256 spp measured 35.0-35.3 ms with the primitives in LDS, 34.3-34.4 without and
-  // 30.3-30.4 without them in the staged form (run_chunks; profiles/r7b/ab_stage_c2.jsonl).
+  // 30.3-30.4 without them in the staged form (run_wavefront; profiles/r7b/ab_stage_c2.jsonl).
   if (rs.fwd && req->sampler == IZPI_SAMPLER_COLOUR && ctx->matset == 0 && sp.staged == 1 && !plan.rec_pool && !plan.time &&
       !plan.cold && !(tu.flags & IZPI_TUNE_NO_SHADE_STAGE))
     sp.prims_staged = 0;
@@ -693,8 +693,9 @@ int render_body(izpi_ctx* ctx, const izpi_render_req* req, const RenderCall& cal
     stage_tables(ctx, req, tu, rs, plan, nbg, sc, sp);
   }
 
-  float trace_ms = 0, shade_ms = 0, tail_ms = 0, total_ms = 0;
-  uint32_t launches = 0;
+  const RunInput run{num_pixels, plan.chunk, plan.pool_blocks, sr};
+  RunTimes times;
+  float total_ms = 0;
   const double t_launch = host_ms();
   HIP_TRY(hipEventRecord(ctx->ev0, st));
   if (pass_log) {  // diagnostics: the GPU time of the setup copies before ev0
@@ -706,14 +707,16 @@ int render_body(izpi_ctx* ctx, const izpi_render_req* req, const RenderCall& cal
   }
   if (rs.preview) {
     const PreviewParams pp = preview_params(ctx, req, plan);
-    rc = run_preview(ctx, req, sc, tr, sp, pp, ap, num_pixels, plan.chunk, sr, &trace_ms, &shade_ms, &launches);
+    rc = run_preview(ctx, req, sc, tr, sp, pp, ap, run, &times);
   } else {
     WaveParams wp = wave_params(ctx, plan, sp);
-#define IZPI_RUN(S, F) run_sampler<S, F>(ctx, req, sc, tr, sp, wp, ap, num_pixels, plan.chunk, plan.pool_blocks, plan.compact, sr, \
-                                        &trace_ms, &shade_ms, &tail_ms, &launches)
-    if (req->sampler == IZPI_SAMPLER_COLOUR) rc = rs.fwd ? IZPI_RUN(IZPI_SAMPLER_COLOUR, true) : IZPI_RUN(IZPI_SAMPLER_COLOUR, false);
-    else rc = rs.fwd ? IZPI_RUN(IZPI_SAMPLER_SPECTRAL, true) : IZPI_RUN(IZPI_SAMPLER_SPECTRAL, false);
-#undef IZPI_RUN
+    // the instance izpi_gpu_upload_scene resolved and prepared (check_request: the scene has the sampler's textures)
+    const ShadeKernels* k = ctx->kernels[req->sampler == IZPI_SAMPLER_SPECTRAL][rs.fwd];
+    if (!k || (!rs.fwd && k->rec_doubles != plan.D)) {  // (the planner derives the record stride on its own)
+      ctx->err = "the shading instance and the workspace plan disagree on the record stride";
+      return IZPI_ERR_INVALID;
+    }
+    rc = run_wavefront(ctx, req, sc, tr, *k, sp, wp, ap, run, &times);
   }
   if (rc) return rc;
   // End frame: the per-wave counter rows summed, the request's post-processing, then the
@@ -738,7 +741,7 @@ int render_body(izpi_ctx* ctx, const izpi_render_req* req, const RenderCall& cal
   s.rays = cnt[CNT_RAYS]; s.node_visits = cnt[CNT_NODES]; s.tri_tests = cnt[CNT_TRI]; s.sph_tests = cnt[CNT_SPH];
   s.light_tri_tests = cnt[CNT_LTRI]; s.light_sph_tests = cnt[CNT_LSPH];
   s.samples = (uint64_t)num_pixels * sr.end;
-  s.kernel_ms = trace_ms; s.shade_ms = shade_ms; s.total_ms = total_ms; s.launches = launches; s.tail_ms = tail_ms;
+  s.kernel_ms = times.trace_ms; s.shade_ms = times.shade_ms; s.total_ms = total_ms; s.launches = times.launches; s.tail_ms = times.tail_ms;
   s.node_steps = cnt[CNT_NSTEP]; s.prim_steps = cnt[CNT_PSTEP]; s.leaf_shortcuts = cnt[CNT_SHORT];
   s.tail_node_visits = cnt[CNT_TAIL_NODES]; s.tail_tri_tests = cnt[CNT_TAIL_TRI]; s.tail_sph_tests = cnt[CNT_TAIL_SPH];
   s.parks = cnt[CNT_PARK];
@@ -1089,11 +1092,14 @@ int upload_packed(izpi_ctx* ctx, const izpi_scene_desc* d, const PackedScene& ps
   // kernel's code object, 14 ms of a fresh renderer's first frame otherwise.
   Tracer tr;
   int rc = make_tracer(ctx, kDefaultTuning, !ctx->sc.tri_only || ctx->any_uv, &tr);
-  const bool compact = ctx->basic_materials && ctx->const_albedo;
-  if (!rc && ctx->mat_ok_rgb) rc = prepare_sampler<IZPI_SAMPLER_COLOUR, true>(ctx, compact);
-  if (!rc && ctx->mat_ok_rgb) rc = prepare_sampler<IZPI_SAMPLER_COLOUR, false>(ctx, compact);
-  if (!rc && ctx->mat_ok_spectral) rc = prepare_sampler<IZPI_SAMPLER_SPECTRAL, true>(ctx, false);
-  if (!rc && ctx->mat_ok_spectral) rc = prepare_sampler<IZPI_SAMPLER_SPECTRAL, false>(ctx, false);
+  const bool const_basic = ctx->basic_materials && ctx->const_albedo;
+  for (int s = 0; s < 2; s++)    // Colour, Spectral
+    for (int f = 1; f >= 0; f--) {  // forward, recursive
+      const uint32_t sampler = s ? IZPI_SAMPLER_SPECTRAL : IZPI_SAMPLER_COLOUR;
+      const ShadeKernels*& k = ctx->kernels[s][f];
+      k = (s ? ctx->mat_ok_spectral : ctx->mat_ok_rgb) ? shade_instance(ctx->matset, const_basic, sampler, f != 0) : nullptr;
+      if (!rc && k) rc = prepare_wavefront(ctx, *k);
+    }
   if (!rc) rc = prepare_preview(ctx);
   return rc;
 }

@@ -1,6 +1,9 @@
 // izpi_kern.h — internal header of libizpi_gpu.so, shared by its HIP translation units:
 //   trace.hip     k_trace2 (BVH4.Hit) and its instance selection;
-//   shade.hip     k_start / k_shade / k_tail / k_accumulate and the wavefront pass loop;
+//   shade_*.hip   (shade.h) k_start / k_shade / k_tail / k_refill, one unit per (sampler,
+//                 accumulation); each hands its kernels out as ShadeKernels tables;
+//   wavefront.hip the shading instance of a scene, the wavefront pass loop over a table,
+//                 k_accumulate and the other small kernels of the loop (plain host code);
 //   preview.hip   k_preview_start / k_preview: the Normal, Albedo and WireFrame samplers;
 //   izpi_gpu.hip  the C ABI, the context, scene upload, the render call, multi-GPU
 //                 (render_plan.cpp: its workspace plan, plain C++).
@@ -1438,7 +1441,26 @@ struct AccumParams {
   double* running;        // [num_pixels][3]
   double* out;
 };
-// The samples one run of the chunk loops renders (run_chunks, run_preview). A one-shot render:
+// The kernels of one shading instance (sampler, accumulation, material set), as the pass loop
+// launches them (wavefront.hip), and what the host needs to know of the instance.
+struct ShadeKernels {
+  using Shade = void (*)(DevScene, ShadeParams, WaveParams);
+  using Tail = void (*)(DevScene, ShadeParams, WaveParams, int32_t*);
+  Shade shade, shade_staged;  // k_shade and its staged form (null when the instance has none)
+  Tail tail32, tail64;        // k_tail<..., 32 / 64, ...>
+  Shade start;                // k_start, the recursion's first fill (null for forward)
+  void (*refill)(DevScene, ShadeParams, WaveParams, const uint32_t*);  // k_refill (null for the recursion)
+  uint32_t sampler, rec_doubles;  // rec_doubles: RecLayout<sampler, matset>::D
+  int matset;
+  bool fwd;
+  char name[24];              // "colour/fwd/SURF"
+};
+// shade_*.hip (shade.h): the tables of (SAMPLER, FWD), one explicit instance per translation
+// unit; null for a material set the pair has no instance of.
+template <int SAMPLER, bool FWD>
+const ShadeKernels* shade_kernels(int matset);
+
+// The samples one run of the chunk loops renders (run_wavefront, run_preview). A one-shot render:
 // [0, req->spp), and the chunk that ends it divides and scatters (AccumParams::last). A step
 // of a progressive session: [begin, end) with keep set: every chunk is folded into the running
 // sums with last = 0, and k_resolve reads them.
@@ -1541,6 +1563,9 @@ struct izpi_ctx {
   uint32_t matset = 0;           // MS_* bits of the scene's material kinds
   bool const_albedo = false;     // ... and every albedo / emit texture a constant RGB: MATSET_CONST (Colour)
   bool any_uv = false;           // a material reads the hit's (u, v) (image textures)
+  // The scene's shading instances, [Spectral][forward] (shade_instance, resolved at upload: what
+  // is prepared is what renders); null where the scene lacks the sampler's textures.
+  const ShadeKernels* kernels[2][2] = {};
   uint32_t pool_grow = 0;        // overflow pool doublings earned by frames that parked (render_impl)
   uint32_t dev_share = 1;        // contexts of this process on this device (izpi_gpu_multi_open): they split its HBM
   // Progress of the running render (izpi_gpu_progress, read from other threads): samples
@@ -1609,17 +1634,22 @@ const izpi_render_tuning kDefaultTuning{};
 // launch it for one pass.
 int make_tracer(izpi_ctx* ctx, const izpi_render_tuning& tu, bool need_uv, Tracer* t);
 void launch_trace(izpi_ctx* ctx, const DevScene& sc, const Tracer& t, const WaveParams& wp, hipStream_t st, int32_t* spill);
-// shade_*.hip (shade.h): every chunk of the request through the wavefront passes with the
-// shading instance of (SAMPLER, FWD) and the scene's material set; one explicit instance per
-// translation unit. Device times of the passes are added to *trace_ms / *shade_ms / *tail_ms.
-template <int SAMPLER, bool FWD>
-int run_sampler(izpi_ctx* ctx, const izpi_render_req* req, const DevScene& sc, const Tracer& tr, ShadeParams& sp,
-                WaveParams& wp, AccumParams& ap, uint32_t num_pixels, uint32_t chunk, uint32_t pool_blocks, bool compact,
-                const SampleRange& sr, float* trace_ms, float* shade_ms, float* tail_ms, uint32_t* launches);
-// shade_*.hip: load the code of the shading kernels run_sampler<SAMPLER, FWD> would launch
-// for the uploaded scene (izpi_gpu_upload_scene, ahead of the first frame).
-template <int SAMPLER, bool FWD>
-int prepare_sampler(izpi_ctx* ctx, bool compact);
+// What a run of the chunk loops (run_wavefront, run_preview) is given: the pixels of the request's
+// tiles, the samples per pixel and chunk, the overflow record blocks (the path samplers), the
+// sample range; and what it reports: the device times of its passes and their number.
+struct RunInput { uint32_t num_pixels, chunk, pool_blocks; SampleRange range; };
+struct RunTimes { float trace_ms = 0, shade_ms = 0, tail_ms = 0; uint32_t launches = 0; };
+// wavefront.hip: the shading instance a scene runs, the smallest that holds its material kinds
+// (matset: its MS_* bits; const_basic: Lambertian + DiffuseLight with constant albedos, whose
+// recursive Colour renders write compact records); every chunk of the request through the
+// wavefront passes with the kernels of k; the code of those kernels (and of k_accumulate)
+// loaded ahead of the first frame (izpi_gpu_upload_scene); k_accumulate's launch.
+const ShadeKernels* shade_instance(uint32_t matset, bool const_basic, uint32_t sampler, bool fwd);
+int run_wavefront(izpi_ctx* ctx, const izpi_render_req* req, const DevScene& sc, const Tracer& tr, const ShadeKernels& k,
+                  ShadeParams& sp, WaveParams& wp, AccumParams& ap, const RunInput& in, RunTimes* out);
+int prepare_wavefront(izpi_ctx* ctx, const ShadeKernels& k);
+int prepare_accumulate(izpi_ctx* ctx);
+void launch_accumulate(hipStream_t st, const AccumParams& ap);
 // preview.hip: the Normal, Albedo and WireFrame samplers (sampler/normal.go, albedo.go,
 // wireframe.go): one primary ray per sample, no path state. The request's units run in
 // batches of `slots`: k_preview_start writes the batch's camera rays into `buf` (start_path),
@@ -1634,8 +1664,7 @@ struct PreviewParams {
   uint32_t slots;         // entries of buf
 };
 int run_preview(izpi_ctx* ctx, const izpi_render_req* req, const DevScene& sc, const Tracer& tr, ShadeParams& sp,
-                const PreviewParams& pp, AccumParams& ap, uint32_t num_pixels, uint32_t chunk, const SampleRange& sr,
-                float* trace_ms, float* shade_ms, uint32_t* launches);
+                const PreviewParams& pp, AccumParams& ap, const RunInput& in, RunTimes* out);
 // preview.hip: load the code of the preview kernels (izpi_gpu_upload_scene)
 int prepare_preview(izpi_ctx* ctx);
 inline bool preview_sampler(uint32_t s) {

@@ -2,7 +2,7 @@
 // albedo.go:30-36, wireframe.go:34-40) under render/rgb.go:27-41's pixel loop: k_preview_start,
 // k_preview and the batch loop that drives them with k_trace2 (run_preview, izpi_kern.h). A
 // translation unit of its own, so the four shade_*.hip units compile what they compiled before.
-#include "shade.h"
+#include "izpi_kern.h"
 
 namespace {
 
@@ -111,9 +111,10 @@ void launch_preview(hipStream_t st, const DevScene& sc, const ShadeParams& sp, c
 }  // namespace
 
 int run_preview(izpi_ctx* ctx, const izpi_render_req* req, const DevScene& sc, const Tracer& tr, ShadeParams& sp,
-                const PreviewParams& pp, AccumParams& ap, uint32_t num_pixels, uint32_t chunk, const SampleRange& sr,
-                float* trace_ms, float* shade_ms, uint32_t* launches) {
+                const PreviewParams& pp, AccumParams& ap, const RunInput& in, RunTimes* out) {
   hipStream_t st = ctx->stream;
+  const uint32_t num_pixels = in.num_pixels, chunk = in.chunk;
+  const SampleRange& sr = in.range;
   if ((uint32_t)tr.blocks * 4 > ctx->num_cus * CPART_BLOCKS_PER_CU * 4) {
     ctx->err = "grid larger than the counter rows";
     return IZPI_ERR_INVALID;
@@ -156,15 +157,15 @@ int run_preview(izpi_ctx* ctx, const izpi_render_req* req, const DevScene& sc, c
       for (int k = 0; k < (wire ? 4 : 2); k++) {
         float ms = 0;
         HIP_TRY(hipEventElapsedTime(&ms, ctx->evb[k], ctx->evb[k + 1]));
-        *((k & 1) ? shade_ms : trace_ms) += ms;
+        ((k & 1) ? out->shade_ms : out->trace_ms) += ms;
       }
-      *launches += wire ? 2u : 1u;
+      out->launches += wire ? 2u : 1u;
       ctx->prog_done.store((uint64_t)s0 * num_pixels + base + n, std::memory_order_relaxed);
     }
     ap.chunk_spp = cs;
     ap.raw_spectral = 0;
     ap.last = (!sr.keep && s0 + cs >= sr.end) ? 1u : 0u;
-    hipLaunchKernelGGL(k_accumulate, dim3((num_pixels + 255) / 256), dim3(256), 0, st, ap);
+    launch_accumulate(st, ap);
     HIP_TRY(hipGetLastError());
   }
   return IZPI_OK;
@@ -177,5 +178,5 @@ int prepare_preview(izpi_ctx* ctx) {
   if ((rc = resident_blocks(ctx, k_preview<PV_ALBEDO>, &blocks))) return rc;
   if ((rc = resident_blocks(ctx, k_preview<PV_WIRE_FIRST>, &blocks))) return rc;
   if ((rc = resident_blocks(ctx, k_preview<PV_WIRE_EDGE>, &blocks))) return rc;
-  return resident_blocks(ctx, k_accumulate, &blocks);
+  return prepare_accumulate(ctx);
 }

@@ -1,7 +1,4 @@
 // shade_colour_fwd.hip — the shading kernels of the Colour sampler, forward (IZPI_ACC_FORWARD) accumulation (shade.h).
 #include "shade.h"
 
-template int run_sampler<IZPI_SAMPLER_COLOUR, true>(izpi_ctx*, const izpi_render_req*, const DevScene&, const Tracer&, ShadeParams&,
-                                 WaveParams&, AccumParams&, uint32_t, uint32_t, uint32_t, bool, const SampleRange&, float*, float*, float*,
-                                 uint32_t*);
-template int prepare_sampler<IZPI_SAMPLER_COLOUR, true>(izpi_ctx*, bool);
+template const ShadeKernels* shade_kernels<IZPI_SAMPLER_COLOUR, true>(int);
