@@ -286,6 +286,46 @@ int izpi_gpu_spectral_post(izpi_ctx* ctx, const double* xyz_dev, double* rgba_de
 int izpi_gpu_postprocess(izpi_ctx* ctx, double* canvas_dev, uint32_t width, uint32_t height, const uint32_t* filters,
                          const double* params, uint32_t num_filters);
 
+/* ---- Denoising a low-sample frame ---------------------------
+ * An edge-avoiding a-trous wavelet filter (Dammertz, Sewtz, Hanika, Lensch, HPG 2010) over
+ * a W*H*4 float64 canvas in Render's layout, with the Normal and Albedo frames of the same
+ * view as edge-stopping guides (they share the Colour frame's primary rays, DESIGN 3.3a, so
+ * they line up with it pixel for pixel). The project's own rule, not the reference's.
+ *
+ * Iteration i = 0..iterations-1 is a 5 x 5 B3-spline kernel with taps `1 << i` pixels apart;
+ * a tap weighs h * exp(-(dc / (sigma_colour / 2^i)^2 + dn / sigma_normal^2 + da /
+ * sigma_albedo^2)) with dc, dn, da the squared RGB distances to the centre in the three
+ * frames. Pixels with alpha 0 (row 0, pixels outside the tiles) or a non-finite colour are
+ * neither read as taps nor changed. Alpha is the centre's. iterations is 0..8 (0 copies);
+ * every sigma is > 0 and may be +Inf (its term drops out); flags is 0. Anything else is
+ * IZPI_ERR_INVALID. p == NULL: the defaults below. normal / albedo may be NULL: the term is
+ * left out. out may not overlap an input; width and height are at least 1.
+ *
+ *  _denoise_device  all four canvases in device memory. Keeps one scratch canvas with the
+ *                   context (it only grows) and ping-pongs so that the last iteration
+ *                   lands in out_dev; returns after the stream has finished. *device_ms
+ *                   (may be NULL): HIP-event time over the iterations. Needs no scene, and
+ *                   touches none of a progressive session's workspace, so it is allowed
+ *                   while one is open: a viewer denoises _snapshot_device output this way.
+ *  _denoise         the same over host memory: upload, _denoise_device, download.
+ *  izpi_host_denoise (izpi_host.h) is the twin on the host, bit for bit.
+ * Multi-GPU callers run it on izpi_gpu_multi_context(m, 0) over the gathered canvas. */
+typedef struct izpi_denoise_params {
+  uint32_t iterations;
+  uint32_t flags; /* 0 */
+  double sigma_colour, sigma_normal, sigma_albedo;
+} izpi_denoise_params;
+#define IZPI_DENOISE_MAX_ITERATIONS 8
+#define IZPI_DENOISE_DEFAULT_ITERATIONS 5 /* sigma defaults 1.0, 0.5, 0.5: see DESIGN 3.8 */
+#define IZPI_DENOISE_DEFAULT_SIGMA_COLOUR 1.0
+#define IZPI_DENOISE_DEFAULT_SIGMA_NORMAL 0.5
+#define IZPI_DENOISE_DEFAULT_SIGMA_ALBEDO 0.5
+int izpi_gpu_denoise_device(izpi_ctx* ctx, const double* colour_dev, const double* normal_dev, const double* albedo_dev,
+                            double* out_dev, uint32_t width, uint32_t height, const izpi_denoise_params* p,
+                            double* device_ms);
+int izpi_gpu_denoise(izpi_ctx* ctx, const double* colour, const double* normal, const double* albedo, double* out,
+                     uint32_t width, uint32_t height, const izpi_denoise_params* p, double* device_ms);
+
 /* GPU BVH4 builder: Morton codes and a radix sort, then a binary
  * tree (method: IZPI_BVH_PLOC clustering or IZPI_BVH_LBVH radix tree), collapsed to
  * 4-wide nodes with collectChildren's rule (or, with IZPI_BVH_SAH, the collapse of least

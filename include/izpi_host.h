@@ -171,10 +171,17 @@ int izpi_host_displace(const izpi_tri_in* tris, uint64_t n, const double* rgba, 
                        double dmin, double dmax, uint32_t order, izpi_tri_in* out, uint64_t cap, uint64_t* n_out,
                        uint64_t* counts, double* ms);
 
+/* The host twin of izpi_gpu_denoise (izpi_gpu.h: the rule and the arguments are the same):
+ * the sequential restatement from the same arithmetic (izpi_amd/csrc/denoise.h), bit for
+ * bit what the device writes. All pointers host; its error is izpi_host_last_error's. */
+int izpi_host_denoise(const double* colour, const double* normal, const double* albedo, double* out, uint32_t width,
+                      uint32_t height, const izpi_denoise_params* p);
+
 /* sizeof() of the boundary structs: 0 izpi_bvh4_node 1 izpi_texture 2 izpi_material
  * 3 izpi_camera 4 izpi_scene_desc 5 izpi_render_req 6 izpi_render_stats 7 izpi_hit
  * 8 izpi_tri_in 9 izpi_sphere_in 10 izpi_camera_in 11 izpi_scene_input 12 izpi_proto_info
- * 13 izpi_obj_info 14 izpi_obj_group 15 izpi_obj_material (0 = unknown). */
+ * 13 izpi_obj_info 14 izpi_obj_group 15 izpi_obj_material 16 izpi_render_tuning
+ * 17 izpi_denoise_params (0 = unknown). */
 uint32_t izpi_abi_struct_size(int which);
 
 /* ======================================================================

@@ -36,6 +36,9 @@ BVH_SAH = 0x100  # flag: collapse by the surface-area cost model (PLOC only)
 BVH_PLOC_SAH = BVH_PLOC | BVH_SAH
 DISPLACE_PER_TRIANGLE, DISPLACE_MESH = 0, 1
 DISPLACE_MAX_LEVELS = 16
+DENOISE_MAX_ITERATIONS = 8
+DENOISE_DEFAULT_ITERATIONS = 5
+DENOISE_DEFAULT_SIGMA_COLOUR, DENOISE_DEFAULT_SIGMA_NORMAL, DENOISE_DEFAULT_SIGMA_ALBEDO = 1.0, 0.5, 0.5
 
 
 def prim_ref(kind, idx):
@@ -136,6 +139,17 @@ class RenderStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
 
 
+class DenoiseParams(C.Structure):
+    _fields_ = [("iterations", C.c_uint32), ("flags", C.c_uint32), ("sigma_colour", C.c_double),
+                ("sigma_normal", C.c_double), ("sigma_albedo", C.c_double)]
+
+
+def denoise_params(iterations=DENOISE_DEFAULT_ITERATIONS, sigma_colour=DENOISE_DEFAULT_SIGMA_COLOUR,
+                   sigma_normal=DENOISE_DEFAULT_SIGMA_NORMAL, sigma_albedo=DENOISE_DEFAULT_SIGMA_ALBEDO):
+    """izpi_denoise_params; the defaults are the library's (what a NULL pointer means)."""
+    return DenoiseParams(int(iterations), 0, float(sigma_colour), float(sigma_normal), float(sigma_albedo))
+
+
 class Hit(C.Structure):
     _fields_ = [("t", C.c_double), ("u", C.c_double), ("v", C.c_double), ("p", C.c_double * 3),
                 ("normal", C.c_double * 3), ("prim_ref", C.c_uint32), ("hit", C.c_uint32)]
@@ -200,7 +214,7 @@ class ObjMaterial(C.Structure):
 
 
 ABI_STRUCTS = [BVH4Node, Texture, Material, Camera, SceneDesc, RenderReq, RenderStats, Hit, TriIn, SphereIn, CameraIn,
-               SceneInput, ProtoInfo, ObjInfo, ObjGroup, ObjMaterial, RenderTuning]
+               SceneInput, ProtoInfo, ObjInfo, ObjGroup, ObjMaterial, RenderTuning, DenoiseParams]
 
 # Symbols include/izpi_gpu.h and include/izpi_host.h declare (checked by tests).
 EXPORTS = [
@@ -224,6 +238,7 @@ EXPORTS = [
     "izpi_gpu_progressive_snapshot_device", "izpi_gpu_progressive_end",
     "izpi_gpu_multi_progressive_begin", "izpi_gpu_multi_progressive_step", "izpi_gpu_multi_progressive_snapshot",
     "izpi_gpu_multi_progressive_end",
+    "izpi_gpu_denoise_device", "izpi_gpu_denoise", "izpi_host_denoise",
 ]
 
 _lib = None
@@ -331,6 +346,10 @@ def lib():
                      C.c_uint64, c_uint64_p, c_uint64_p, c_double_p]
     L.izpi_host_displace.argtypes = displace_args
     L.izpi_gpu_displace.argtypes = [vp] + displace_args
+    denoise_args = [vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams)]  # colour, normal, albedo, out
+    L.izpi_host_denoise.argtypes = denoise_args
+    L.izpi_gpu_denoise.argtypes = [vp] + denoise_args + [c_double_p]
+    L.izpi_gpu_denoise_device.argtypes = [vp] + denoise_args + [c_double_p]
     L.izpi_scene_add_triangles.argtypes = [vp, vp, C.c_uint64, C.c_char_p]
     L.izpi_scene_background.argtypes = [vp, c_double_p, c_double_p, C.c_uint32]
     L.izpi_scene_background.restype = C.c_uint32

@@ -611,6 +611,7 @@ uint32_t izpi_abi_struct_size(int which) {
     case 14: return sizeof(izpi_obj_group);
     case 15: return sizeof(izpi_obj_material);
     case 16: return sizeof(izpi_render_tuning);
+    case 17: return sizeof(izpi_denoise_params);
   }
   return 0;
 }

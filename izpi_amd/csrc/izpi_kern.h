@@ -6,7 +6,8 @@
 //                 k_accumulate and the other small kernels of the loop (plain host code);
 //   preview.hip   k_preview_start / k_preview: the Normal, Albedo and WireFrame samplers;
 //   izpi_gpu.hip  the C ABI, the context, scene upload, the render call, multi-GPU
-//                 (render_plan.cpp: its workspace plan, plain C++).
+//                 (render_plan.cpp: its workspace plan, plain C++);
+//   denoise.hip   k_denoise and the izpi_gpu_denoise entries (denoise.h: the arithmetic).
 // Device helpers (textures, spectra, the wavefront state, hit records, lights, materials,
 // the shading records) and the host context live here. Not part of the ABI.
 #pragma once
@@ -1546,6 +1547,7 @@ struct izpi_ctx {
   double* d_post = nullptr; size_t post_cap = 0;      // spectral post-processing output
   double* d_share = nullptr; size_t share_cap = 0;    // multi-GPU: this device's packed tiles
   double* d_gather = nullptr; size_t gather_cap = 0;  // multi-GPU root: every device's packed tiles
+  double* d_denoise = nullptr; size_t denoise_cap = 0;  // izpi_gpu_denoise_device's scratch canvas (denoise.hip; it only grows)
   uint32_t* h_count = nullptr;                        // pinned readback of d_misc (unit head, queue lengths; same stride) + scratch
   hipEvent_t ev3 = nullptr;
   hipEvent_t evb[3 * IZPI_PASS_BATCH] = {};

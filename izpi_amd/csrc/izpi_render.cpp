@@ -8,6 +8,14 @@
 //               [--device 0 | --gpus N] [--seed 12345]
 //               [--sampler colour|normal|wireframe|albedo|spectral] [--ink r,g,b]
 //               [--progressive STEP [--snapshots PREFIX]]
+//               [--denoise [N] [--denoise-sigma c,n,a]]
+//
+// --denoise [N] (--sampler colour or spectral) filters the frame with N iterations (default
+// IZPI_DENOISE_DEFAULT_ITERATIONS) of the edge-avoiding a-trous denoiser (izpi_gpu_denoise,
+// DESIGN.md section 3.8): the frame, a Normal frame and, for the Colour sampler, an Albedo
+// frame (the guides at 4 samples) are rendered to host memory and filtered on the device;
+// --out / --raw get the filtered canvas. --denoise-sigma sets sigma_colour, sigma_normal
+// and sigma_albedo (defaults 1, 0.5, 0.5).
 //
 // --progressive STEP renders the frame in steps of STEP samples per pixel (a progressive
 // session, izpi_gpu_progressive_*) and --snapshots PREFIX writes PREFIX_<done>.pfm after each
@@ -80,6 +88,9 @@ void write_pfm(const std::string& path, const std::vector<double>& canvas, uint3
 int main(int argc, char** argv) {
   std::string scene_path, obj_path, obj_material = "White", out_pfm, out_raw, bvh = "gpu", acc = "forward", sampler_name, snap_prefix;
   uint32_t progressive = 0;
+  bool denoise = false;
+  izpi_denoise_params dparams = {IZPI_DENOISE_DEFAULT_ITERATIONS, 0, IZPI_DENOISE_DEFAULT_SIGMA_COLOUR,
+                                 IZPI_DENOISE_DEFAULT_SIGMA_NORMAL, IZPI_DENOISE_DEFAULT_SIGMA_ALBEDO};
   double ink[3] = {0.0, 0.0, 0.0};
   bool quantized = false;
   uint32_t W = 1024, H = 1024, spp = 16, depth = 50, device = 0, gpus = 1;
@@ -107,6 +118,14 @@ int main(int argc, char** argv) {
     else if (a == "--sampler") sampler_name = val();
     else if (a == "--progressive") { progressive = (uint32_t)atoi(val().c_str()); if (!progressive) die("--progressive takes a step of at least 1 sample"); }
     else if (a == "--snapshots") snap_prefix = val();
+    else if (a == "--denoise") {
+      denoise = true;
+      if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') dparams.iterations = (uint32_t)atoi(argv[++i]);
+    }
+    else if (a == "--denoise-sigma") {
+      if (sscanf(val().c_str(), "%lf,%lf,%lf", &dparams.sigma_colour, &dparams.sigma_normal, &dparams.sigma_albedo) != 3)
+        die("--denoise-sigma takes colour,normal,albedo");
+    }
     else if (a == "--ink") { if (sscanf(val().c_str(), "%lf,%lf,%lf", &ink[0], &ink[1], &ink[2]) != 3) die("--ink takes r,g,b"); }
     else die("unknown option " + a);
   }
@@ -157,6 +176,9 @@ int main(int argc, char** argv) {
   else if (!sampler_name.empty()) die("--sampler must be colour, normal, wireframe, albedo or spectral");
   else sampler_name = sampler == IZPI_SAMPLER_SPECTRAL ? "spectral" : "colour";
   const bool spectral = sampler == IZPI_SAMPLER_SPECTRAL;
+  if (denoise && sampler != IZPI_SAMPLER_COLOUR && !spectral) die("--denoise needs --sampler colour or spectral");
+  if (denoise && progressive) die("--denoise filters a whole frame: not with --progressive");
+  if (denoise && png) die("--denoise filters linear values: not with --png-pipeline");
   // ---- transport.ToScene, BVH, upload
   auto t0 = std::chrono::steady_clock::now();
   const izpi_scene_input* in = nullptr;
@@ -227,6 +249,27 @@ int main(int argc, char** argv) {
     if (izpi_gpu_multi_render(multi, &req, canvas.data(), stv.data())) die(izpi_gpu_multi_last_error(multi));
   } else if (izpi_gpu_render(ctx, &req, canvas.data(), stv.data())) {
     die(izpi_gpu_last_error(ctx));
+  }
+  if (denoise) {
+    // the guides share the frame's primary rays (same seed, same streams), then the filter
+    std::vector<double> normal(canvas.size()), albedo(spectral ? 0 : canvas.size()), filtered(canvas.size());
+    std::vector<izpi_render_stats> gst(stv.size());
+    izpi_render_req g = req;
+    g.post = IZPI_POST_NONE;
+    g.spp = 4;  // render_denoised's aov_spp
+    auto guide = [&](uint32_t which, std::vector<double>& into) {
+      g.sampler = which;
+      if (multi ? izpi_gpu_multi_render(multi, &g, into.data(), gst.data()) : izpi_gpu_render(ctx, &g, into.data(), gst.data()))
+        die(multi ? izpi_gpu_multi_last_error(multi) : izpi_gpu_last_error(ctx));
+    };
+    guide(IZPI_SAMPLER_NORMAL, normal);
+    if (!spectral) guide(IZPI_SAMPLER_ALBEDO, albedo);
+    double ms = 0;
+    if (izpi_gpu_denoise(ctx, canvas.data(), normal.data(), spectral ? nullptr : albedo.data(), filtered.data(), W, H,
+                         &dparams, &ms))
+      die(izpi_gpu_last_error(ctx));
+    canvas.swap(filtered);
+    fprintf(stderr, "izpi-render: denoised, %u iterations, %.3f ms on the device\n", dparams.iterations, ms);
   }
   izpi_render_stats st = stv[0];
   for (size_t i = 1; i < stv.size(); i++) { st.rays += stv[i].rays; st.node_visits += stv[i].node_visits; }

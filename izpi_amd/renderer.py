@@ -62,6 +62,64 @@ def build_bvh4(ctx, boxes, leaf_max=4, method=None):
     return nodes[:m.value].copy(), order[:n].copy(), ms.value
 
 
+def _canvas_args(colour, normal, albedo):
+    """The three input canvases as contiguous (H, W, 4) float64 arrays (guides may be None)."""
+    colour = np.ascontiguousarray(colour, np.float64)
+    if colour.ndim != 3 or colour.shape[2] != 4:
+        raise ValueError("a canvas is (H, W, 4) float64")
+    guides = []
+    for g in (normal, albedo):
+        if g is not None:
+            g = np.ascontiguousarray(g, np.float64)
+            if g.shape != colour.shape:
+                raise ValueError("the guides have the colour canvas's shape")
+        guides.append(g)
+    return colour, guides[0], guides[1]
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def host_denoise(colour, normal=None, albedo=None, params=None):
+    """izpi_host_denoise: the denoiser's host twin over (H, W, 4) float64
+    canvases; normal / albedo are the guides or None, params an N.DenoiseParams (None = the
+    library's defaults). Returns the denoised canvas. Needs no GPU."""
+    colour, normal, albedo = _canvas_args(colour, normal, albedo)
+    out = np.zeros_like(colour)
+    L = N.lib()
+    rc = L.izpi_host_denoise(_ptr(colour), _ptr(normal), _ptr(albedo), _ptr(out), colour.shape[1], colour.shape[0],
+                             None if params is None else C.byref(params))
+    if rc != 0:
+        raise RuntimeError("izpi_host_denoise failed (status %d): %s" % (rc, L.izpi_host_last_error().decode()))
+    return out
+
+
+def denoise(ctx, colour, normal=None, albedo=None, params=None, timing=None):
+    """izpi_gpu_denoise on context `ctx` over host canvases (upload, filter, download):
+    host_denoise's arguments and result, bit for bit. timing (a dict) receives "ms"."""
+    colour, normal, albedo = _canvas_args(colour, normal, albedo)
+    out = np.zeros_like(colour)
+    ms = C.c_double()
+    _check(N.lib().izpi_gpu_denoise(ctx, _ptr(colour), _ptr(normal), _ptr(albedo), _ptr(out), colour.shape[1],
+                                    colour.shape[0], None if params is None else C.byref(params), C.byref(ms)),
+           ctx, "izpi_gpu_denoise")
+    if timing is not None:
+        timing["ms"] = ms.value
+    return out
+
+
+def denoise_device(ctx, colour_ptr, normal_ptr, albedo_ptr, out_ptr, width, height, params=None):
+    """izpi_gpu_denoise_device on context `ctx`: device pointers (normal_ptr / albedo_ptr may
+    be None); returns the device ms of the iterations."""
+    ms = C.c_double()
+    _check(N.lib().izpi_gpu_denoise_device(ctx, C.c_void_p(colour_ptr), C.c_void_p(normal_ptr or 0),
+                                           C.c_void_p(albedo_ptr or 0), C.c_void_p(out_ptr), width, height,
+                                           None if params is None else C.byref(params), C.byref(ms)),
+           ctx, "izpi_gpu_denoise_device")
+    return ms.value
+
+
 def make_request(width, height, spp, max_depth, sampler, background, seed, exposure, bg_spd=None, tiles=None,
                  layout=N.OUT_CANVAS, post=N.POST_NONE, tuning=None, accumulation=N.ACC_RECURSIVE, ink=(0.0, 0.0, 0.0)):
     """izpi_render_req for Render (the arrays it points to are kept alive on `req._keep`).
@@ -327,6 +385,49 @@ class GPURenderer:
         _check(N.lib().izpi_gpu_postprocess(self.ctx, C.c_void_p(canvas_ptr), self.width, self.height,
                                             k.ctypes.data_as(N.c_uint32_p), p.ctypes.data_as(N.c_double_p), len(k)),
                self.ctx, "izpi_gpu_postprocess")
+
+    def denoise_device(self, colour_ptr, normal_ptr, albedo_ptr, out_ptr, params=None):
+        """izpi_gpu_denoise_device over device canvases of this renderer's size:
+        normal_ptr / albedo_ptr may be None, params is an N.DenoiseParams (None = the library's
+        defaults). Returns the device ms. Allowed while a progressive session is open."""
+        return denoise_device(self.ctx, colour_ptr, normal_ptr, albedo_ptr, out_ptr, self.width, self.height, params)
+
+    def render_denoised(self, spp=None, aov_spp=4, params=None, post=N.POST_NONE, albedo=None):
+        """A denoised frame of this renderer's sampler (Colour, or Spectral through
+        POST_SPECTRAL) at `spp` samples (None: self.spp): the frame, then the Normal frame and
+        (albedo=True; the default for Colour, off for Spectral, whose scenes may carry no RGB
+        albedo) the Albedo frame at `aov_spp`, all into device canvases, then the filter on
+        the linear values, then `post`'s Gamma / Clamp. Returns the host canvas;
+        self.last_noisy keeps the unfiltered frame (before Gamma / Clamp) and
+        self.denoise_ms the filter's device time."""
+        import torch
+        if self.sampler not in (N.SAMPLER_COLOUR, N.SAMPLER_SPECTRAL):
+            raise ValueError("render_denoised needs the Colour or the Spectral sampler")
+        spectral = self.sampler == N.SAMPLER_SPECTRAL
+        if albedo is None:
+            albedo = not spectral
+        dev = torch.device("cuda", self.device)
+        shape = (self.height, self.width, 4)
+        colour = torch.zeros(shape, dtype=torch.float64, device=dev)
+        out = torch.zeros(shape, dtype=torch.float64, device=dev)
+        guides = {name: torch.zeros(shape, dtype=torch.float64, device=dev)
+                  for name in (("normal", "albedo") if albedo else ("normal",))}
+        torch.cuda.synchronize(dev)  # the zero fills run on torch's stream, the library on its own
+        stats = self.render_device(colour.data_ptr(), spp=spp, post=N.POST_SPECTRAL if spectral else N.POST_NONE)
+        own = self.sampler
+        try:
+            for name, canvas in guides.items():
+                self.sampler = N.SAMPLER_NORMAL if name == "normal" else N.SAMPLER_ALBEDO
+                self.render_device(canvas.data_ptr(), spp=aov_spp)
+        finally:
+            self.sampler = own
+        self.stats = stats  # the frame's, not the guides'
+        self.denoise_ms = self.denoise_device(colour.data_ptr(), guides["normal"].data_ptr(),
+                                              guides["albedo"].data_ptr() if albedo else None, out.data_ptr(), params)
+        if post & N.POST_GAMMA_CLAMP:
+            self.postprocess(out.data_ptr(), [(N.FILTER_GAMMA, 0.0), (N.FILTER_CLAMP, 1.0)])
+        self.last_noisy = colour.cpu().numpy()
+        return out.cpu().numpy()
 
     def render_device(self, out_ptr, tiles=None, layout=N.OUT_CANVAS, spp=None, post=N.POST_NONE):
         """Render into device memory at `out_ptr` (e.g. torch tensor .data_ptr())."""
