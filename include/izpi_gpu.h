@@ -447,6 +447,80 @@ int izpi_gpu_multi_progressive_step(izpi_multi* m, uint32_t spp, izpi_render_sta
 int izpi_gpu_multi_progressive_snapshot(izpi_multi* m, uint32_t form, double* out_host);
 int izpi_gpu_multi_progressive_end(izpi_multi* m);
 
+/* ---- The noise estimate of a progressive session (deviation A25) ----
+ * How noisy is the frame, where, and may the caller stop? The project's own rule: the
+ * reference has no such estimate, and no entry above computes it unasked. A session begun
+ * with IZPI_PROG_NOISE keeps, next to each pixel's sums s_c, the second moments of its
+ * samples, m2_c = m2_c + x_c * x_c, folded by the pass that folds the sums, in sample order
+ * (24 B per pixel, a buffer of the context's own that only grows). x is what is added to the
+ * sums: for a forward Spectral render the weighed X, Y, Z. The sums keep their additions: the
+ * CANVAS and DISPLAY snapshots and the counters are those of a session without the flag.
+ *
+ * Per pixel after n = done >= 2 samples (no fused multiply-add anywhere):
+ *   mean_c = the canvas rule: s_c / n (Colour, the preview samplers), s_c * (1 / n) (Spectral)
+ *   v_c    = (m2_c - (s_c * s_c) / n) / (n - 1);  !(v_c > 0) -> 0
+ *   se_c   = sqrt(v_c / n)                        (the standard error of the mean)
+ *   e      = ((se_0 + se_1) + se_2) / (((|mean_0| + |mean_1|) + |mean_2|) + floor)
+ * A pixel is non-finite when a sum, a moment or e is not finite. A pixel is counted when its
+ * sample row y >= 1 (row 0 lands on canvas row H and is dropped: it must not hold a render
+ * open). Over the counted pixels, in packed order p (tile after tile, by y then x):
+ *   pixels, nonfinite, above (finite pixels with e > threshold), max_error (largest finite e),
+ *   sum_error: each block of 256 consecutive p fills v[0..255] with e (+0.0 for a pixel that
+ *   is not counted, not finite, or past the end), adds v[i] = v[i] + v[i + stride] for i <
+ *   stride, stride = 128, 64, ..., 1, and the blocks' v[0] are added in block order.
+ * The integers and the maximum depend on no order; sum_error on the blocking only. The multi
+ * form adds the devices' integers, takes the maximum of their maxima and adds their
+ * sum_error in device order: sum_error (and nothing else) depends on the share plan in its
+ * last bits. converged = done >= min_spp && (double)above <= tolerated * (double)(pixels -
+ * nonfinite).
+ *
+ * The defaults are placeholders from one look at a 40 x 40 Cornell box (forward accumulation,
+ * seed 12345: median e 0.47 at 4 spp, 0.18 at 32). A handful of samples UNDERESTIMATES the
+ * variance wherever most of them are black (the share of pixels above 0.25 rises from 0.59 at
+ * 2 spp to 0.82 at 4 before it falls): min_spp keeps a frame from "converging" on such an
+ * estimate, so do not set it to 2 without a reason.
+ *
+ *  begin_ex   _begin with flags: IZPI_PROG_NOISE or 0 (any other bit: IZPI_ERR_INVALID).
+ *             _begin is _begin_ex(..., 0).
+ *  snapshot   IZPI_SNAP_NOISE (every snapshot entry): (se_0, se_1, se_2, 1.0) per pixel in the
+ *             session's layout, by IZPI_SNAP_CANVAS's row and tile rule, without req->post;
+ *             Spectral values are in XYZ, the sums' space; a non-finite pixel holds what the
+ *             arithmetic gives. IZPI_ERR_INVALID without the flag or with done < 2.
+ *  noise      the frame statistic (p == NULL: the defaults). threshold and floor finite and
+ *             > 0, tolerated in [0, 1], flags 0, a session with the flag and done >= 2: else
+ *             IZPI_ERR_INVALID. device_ms: HIP-event time of the statistic's kernel (the
+ *             multi form: the largest of the devices').
+ *  converge   repeats step(step_spp) then, once done >= max(2, min_spp), noise, until the
+ *             frame is converged or done == N. The decision reads above, pixels and
+ *             nonfinite only: a multi-GPU session stops at the same done as one GPU. stats /
+ *             noise (either may be NULL) are the last step's and the last evaluation's
+ *             (noise->done == 0: none was made). stats of the multi form: [num_devices].
+ * All of them need an open session. izpi_host_noise (izpi_host.h) is the twin on the host. */
+enum { IZPI_PROG_NOISE = 1 };  /* izpi_gpu_progressive_begin_ex's flags */
+enum { IZPI_SNAP_NOISE = 2 };  /* with IZPI_SNAP_CANVAS, IZPI_SNAP_DISPLAY */
+typedef struct izpi_noise_params {
+  double threshold, floor, tolerated;
+  uint32_t min_spp;
+  uint32_t flags; /* 0 */
+} izpi_noise_params;
+#define IZPI_NOISE_DEFAULT_THRESHOLD 0.25 /* placeholders: see above */
+#define IZPI_NOISE_DEFAULT_FLOOR 0.01
+#define IZPI_NOISE_DEFAULT_TOLERATED 0.05
+#define IZPI_NOISE_DEFAULT_MIN_SPP 8
+typedef struct izpi_noise_stats {
+  uint64_t pixels, nonfinite, above;
+  double max_error, sum_error, device_ms;
+  uint32_t done, converged;
+} izpi_noise_stats;
+int izpi_gpu_progressive_begin_ex(izpi_ctx* ctx, const izpi_render_req* req, uint32_t step_spp, uint32_t flags);
+int izpi_gpu_progressive_noise(izpi_ctx* ctx, const izpi_noise_params* p, izpi_noise_stats* out);
+int izpi_gpu_progressive_converge(izpi_ctx* ctx, const izpi_noise_params* p, izpi_render_stats* stats,
+                                  izpi_noise_stats* noise);
+int izpi_gpu_multi_progressive_begin_ex(izpi_multi* m, const izpi_render_req* req, uint32_t step_spp, uint32_t flags);
+int izpi_gpu_multi_progressive_noise(izpi_multi* m, const izpi_noise_params* p, izpi_noise_stats* out);
+int izpi_gpu_multi_progressive_converge(izpi_multi* m, const izpi_noise_params* p, izpi_render_stats* stats,
+                                        izpi_noise_stats* noise);
+
 /* Bytes of device output izpi_gpu_render_device writes for `req`. */
 uint64_t izpi_gpu_output_bytes(const izpi_render_req* req);
 

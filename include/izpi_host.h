@@ -177,11 +177,22 @@ int izpi_host_displace(const izpi_tri_in* tris, uint64_t n, const double* rgba, 
 int izpi_host_denoise(const double* colour, const double* normal, const double* albedo, double* out, uint32_t width,
                       uint32_t height, const izpi_denoise_params* p);
 
+/* The host twin of izpi_gpu_progressive_noise and of the IZPI_SNAP_NOISE snapshot (izpi_gpu.h:
+ * the rule is stated there; the arithmetic is izpi_amd/csrc/noise.h's, bit for bit what the
+ * device gives): sums and moment2 are [num_pixels][3], the per-pixel sums and second moments
+ * after `done` >= 2 samples, in packed order; counted[p] != 0 marks the pixels the statistic
+ * counts (NULL: all); sampler (IZPI_SAMPLER_*) picks the mean's rule; p == NULL: the
+ * defaults. se_out ([num_pixels][4], may be NULL) receives (se_0, se_1, se_2, 1.0) of every
+ * pixel, counted or not; out (may be NULL) the statistic, device_ms 0. Its error is
+ * izpi_host_last_error's. */
+int izpi_host_noise(const double* sums, const double* moment2, const uint8_t* counted, uint32_t num_pixels, uint32_t done,
+                    uint32_t sampler, const izpi_noise_params* p, double* se_out, izpi_noise_stats* out);
+
 /* sizeof() of the boundary structs: 0 izpi_bvh4_node 1 izpi_texture 2 izpi_material
  * 3 izpi_camera 4 izpi_scene_desc 5 izpi_render_req 6 izpi_render_stats 7 izpi_hit
  * 8 izpi_tri_in 9 izpi_sphere_in 10 izpi_camera_in 11 izpi_scene_input 12 izpi_proto_info
  * 13 izpi_obj_info 14 izpi_obj_group 15 izpi_obj_material 16 izpi_render_tuning
- * 17 izpi_denoise_params (0 = unknown). */
+ * 17 izpi_denoise_params 18 izpi_noise_params 19 izpi_noise_stats (0 = unknown). */
 uint32_t izpi_abi_struct_size(int which);
 
 /* ======================================================================

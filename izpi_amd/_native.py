@@ -27,7 +27,10 @@ MATF_BEER_LAMBERT = 1
 SAMPLER_NORMAL, SAMPLER_COLOUR, SAMPLER_WIREFRAME, SAMPLER_ALBEDO, SAMPLER_SPECTRAL = 1, 2, 3, 4, 5  # sampler.go:13-20
 OUT_CANVAS, OUT_PACKED = 0, 1
 POST_NONE, POST_SPECTRAL, POST_GAMMA_CLAMP = 0, 1, 2
-SNAP_CANVAS, SNAP_DISPLAY = 0, 1  # izpi_gpu_progressive_snapshot's forms
+SNAP_CANVAS, SNAP_DISPLAY, SNAP_NOISE = 0, 1, 2  # izpi_gpu_progressive_snapshot's forms
+PROG_NOISE = 1  # izpi_gpu_progressive_begin_ex's flag: keep the samples' second moments
+# placeholders from one look at a 40 x 40 Cornell box (include/izpi_gpu.h says why min_spp exists)
+NOISE_DEFAULT_THRESHOLD, NOISE_DEFAULT_FLOOR, NOISE_DEFAULT_TOLERATED, NOISE_DEFAULT_MIN_SPP = 0.25, 0.01, 0.05, 8
 FILTER_GAMMA, FILTER_CLAMP = 1, 2
 MAX_FILTERS = 8
 HOST_SKIP_BVH = 1
@@ -150,6 +153,26 @@ def denoise_params(iterations=DENOISE_DEFAULT_ITERATIONS, sigma_colour=DENOISE_D
     return DenoiseParams(int(iterations), 0, float(sigma_colour), float(sigma_normal), float(sigma_albedo))
 
 
+class NoiseParams(C.Structure):
+    _fields_ = [("threshold", C.c_double), ("floor", C.c_double), ("tolerated", C.c_double),
+                ("min_spp", C.c_uint32), ("flags", C.c_uint32)]
+
+
+def noise_params(threshold=NOISE_DEFAULT_THRESHOLD, floor=NOISE_DEFAULT_FLOOR, tolerated=NOISE_DEFAULT_TOLERATED,
+                 min_spp=NOISE_DEFAULT_MIN_SPP):
+    """izpi_noise_params; the defaults are the library's (what a NULL pointer means)."""
+    return NoiseParams(float(threshold), float(floor), float(tolerated), int(min_spp), 0)
+
+
+class NoiseStats(C.Structure):
+    _fields_ = [("pixels", C.c_uint64), ("nonfinite", C.c_uint64), ("above", C.c_uint64),
+                ("max_error", C.c_double), ("sum_error", C.c_double), ("device_ms", C.c_double),
+                ("done", C.c_uint32), ("converged", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class Hit(C.Structure):
     _fields_ = [("t", C.c_double), ("u", C.c_double), ("v", C.c_double), ("p", C.c_double * 3),
                 ("normal", C.c_double * 3), ("prim_ref", C.c_uint32), ("hit", C.c_uint32)]
@@ -214,7 +237,7 @@ class ObjMaterial(C.Structure):
 
 
 ABI_STRUCTS = [BVH4Node, Texture, Material, Camera, SceneDesc, RenderReq, RenderStats, Hit, TriIn, SphereIn, CameraIn,
-               SceneInput, ProtoInfo, ObjInfo, ObjGroup, ObjMaterial, RenderTuning, DenoiseParams]
+               SceneInput, ProtoInfo, ObjInfo, ObjGroup, ObjMaterial, RenderTuning, DenoiseParams, NoiseParams, NoiseStats]
 
 # Symbols include/izpi_gpu.h and include/izpi_host.h declare (checked by tests).
 EXPORTS = [
@@ -239,6 +262,9 @@ EXPORTS = [
     "izpi_gpu_multi_progressive_begin", "izpi_gpu_multi_progressive_step", "izpi_gpu_multi_progressive_snapshot",
     "izpi_gpu_multi_progressive_end",
     "izpi_gpu_denoise_device", "izpi_gpu_denoise", "izpi_host_denoise",
+    "izpi_gpu_progressive_begin_ex", "izpi_gpu_progressive_noise", "izpi_gpu_progressive_converge",
+    "izpi_gpu_multi_progressive_begin_ex", "izpi_gpu_multi_progressive_noise", "izpi_gpu_multi_progressive_converge",
+    "izpi_host_noise",
 ]
 
 _lib = None
@@ -298,6 +324,10 @@ def lib():
         getattr(L, pre + "step").argtypes = [C.c_void_p, C.c_uint32, C.POINTER(RenderStats)]
         getattr(L, pre + "snapshot").argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         getattr(L, pre + "end").argtypes = [C.c_void_p]
+        getattr(L, pre + "begin_ex").argtypes = [C.c_void_p, C.POINTER(RenderReq), C.c_uint32, C.c_uint32]
+        getattr(L, pre + "noise").argtypes = [C.c_void_p, C.POINTER(NoiseParams), C.POINTER(NoiseStats)]
+        getattr(L, pre + "converge").argtypes = [C.c_void_p, C.POINTER(NoiseParams), C.POINTER(RenderStats),
+                                                 C.POINTER(NoiseStats)]
     L.izpi_gpu_progressive_snapshot_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
     L.izpi_host_build_scene_ex.argtypes = [C.POINTER(SceneInput), C.c_uint32, C.POINTER(C.c_void_p)]
     L.izpi_host_scene_prim_boxes.argtypes = [C.c_void_p, c_double_p]
@@ -349,6 +379,9 @@ def lib():
     denoise_args = [vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams)]  # colour, normal, albedo, out
     L.izpi_host_denoise.argtypes = denoise_args
     L.izpi_gpu_denoise.argtypes = [vp] + denoise_args + [c_double_p]
+    # sums, moment2, counted, num_pixels, done, sampler, params, se_out, stats
+    L.izpi_host_noise.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(NoiseParams), vp,
+                                  C.POINTER(NoiseStats)]
     L.izpi_gpu_denoise_device.argtypes = [vp] + denoise_args + [c_double_p]
     L.izpi_scene_add_triangles.argtypes = [vp, vp, C.c_uint64, C.c_char_p]
     L.izpi_scene_background.argtypes = [vp, c_double_p, c_double_p, C.c_uint32]

@@ -612,6 +612,8 @@ uint32_t izpi_abi_struct_size(int which) {
     case 15: return sizeof(izpi_obj_material);
     case 16: return sizeof(izpi_render_tuning);
     case 17: return sizeof(izpi_denoise_params);
+    case 18: return sizeof(izpi_noise_params);
+    case 19: return sizeof(izpi_noise_stats);
   }
   return 0;
 }

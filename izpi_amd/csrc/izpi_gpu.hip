@@ -3,6 +3,7 @@
 // (threads and RCCL ranks), post-processing and the component entries. The kernels of the
 // hot path are in trace.hip and shade.hip (izpi_kern.h).
 #include "izpi_kern.h"
+#include "noise.h"
 #include "scene_pack.h"
 
 #include <array>
@@ -252,12 +253,13 @@ struct CtxBuf {
   void** p;
   size_t* cap;
 };
-constexpr size_t RENDER_BUFS = 7, CTX_BUFS = 17;
+constexpr size_t RENDER_BUFS = 7, CTX_BUFS = 19;
 std::array<CtxBuf, CTX_BUFS> ctx_buffers(izpi_ctx* c) {
 #define IZPI_BUF(name) CtxBuf{(void**)&c->d_##name, &c->name##_cap}
   return {IZPI_BUF(samples), IZPI_BUF(recs), IZPI_BUF(pool), IZPI_BUF(ring), IZPI_BUF(running), IZPI_BUF(state),
           IZPI_BUF(spill), IZPI_BUF(out), IZPI_BUF(tiles), IZPI_BUF(utiles), IZPI_BUF(bg), IZPI_BUF(post),
-          IZPI_BUF(share), IZPI_BUF(gather), IZPI_BUF(cpart), IZPI_BUF(finq), IZPI_BUF(denoise)};
+          IZPI_BUF(share), IZPI_BUF(gather), IZPI_BUF(cpart), IZPI_BUF(finq), IZPI_BUF(denoise),
+          IZPI_BUF(moments), IZPI_BUF(noisepart)};
 #undef IZPI_BUF
 }
 uint64_t buffer_bytes(izpi_ctx* ctx, size_t n) {
@@ -892,17 +894,32 @@ void session_drop(izpi_ctx* ctx) {
   ctx->prog_total.store(0, std::memory_order_relaxed);
 }
 
+int session_zero_moments(izpi_ctx* ctx) {
+  izpi_ctx::Session& ss = ctx->session;
+  const size_t bytes = (size_t)ss.num_pixels * 3 * sizeof(double);
+  const int rc = grow(ctx, (void**)&ctx->d_moments, &ctx->moments_cap, bytes);
+  if (rc) return rc;
+  HIP_TRY(hipMemsetAsync(ctx->d_moments, 0, bytes, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  ss.noise = true;
+  return IZPI_OK;
+}
+
 // begin: render_body's own checks, plan and allocation for a request of step_spp samples
 // (its prepare_only form, which for a session also zeroes the sums and the counters).
-int session_begin(izpi_ctx* ctx, const izpi_render_req* req, uint32_t step_spp) {
+// With IZPI_PROG_NOISE the samples' second moments start at zero in a buffer of their own
+// (24 B per pixel; it only grows, and no workspace plan counts it).
+int session_begin(izpi_ctx* ctx, const izpi_render_req* req, uint32_t step_spp, uint32_t flags = 0) {
   if (ctx->session.open) { ctx->err = "a progressive session is already open"; return IZPI_ERR_INVALID; }
   if (!req || step_spp == 0) { ctx->err = "progressive_begin: a request and step_spp >= 1"; return IZPI_ERR_INVALID; }
+  if (flags & ~(uint32_t)IZPI_PROG_NOISE) { ctx->err = "progressive_begin: unknown flags"; return IZPI_ERR_INVALID; }
   izpi_ctx::Session& ss = ctx->session;
   int rc = session_copy_request(ss, req, ctx->err);
   if (!rc) {
     ss.step_spp = std::min(step_spp, std::max(1u, ss.req.spp));
     rc = render_body(ctx, &ss.req, RenderCall{SampleRange{0, 0, true}, ss.step_spp, true}, nullptr);
   }
+  if (!rc && (flags & IZPI_PROG_NOISE)) rc = session_zero_moments(ctx);
   if (rc) {
     const std::string why = ctx->err;
     session_drop(ctx);
@@ -947,18 +964,110 @@ int session_step(izpi_ctx* ctx, uint32_t spp, izpi_render_stats* stats) {
   return IZPI_OK;
 }
 
+// The session's tiles on the device (izpi_gpu_unpack_tiles may have used d_tiles since the last step).
+int session_tiles(izpi_ctx* ctx) {
+  const izpi_ctx::Session& ss = ctx->session;
+  const int rc = grow(ctx, (void**)&ctx->d_tiles, &ctx->tiles_cap, ss.run_tiles.size() * sizeof(uint32_t));
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(ctx->d_tiles, ss.run_tiles.data(), ss.run_tiles.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+  return IZPI_OK;
+}
+
+// The noise estimate needs a session begun with IZPI_PROG_NOISE and two samples (n - 1 divides).
+int session_has_noise(izpi_ctx* ctx) {
+  if (!ctx->session.noise) { ctx->err = "noise: the session was begun without IZPI_PROG_NOISE"; return IZPI_ERR_INVALID; }
+  if (ctx->session.done < 2) { ctx->err = "noise: needs at least 2 samples"; return IZPI_ERR_INVALID; }
+  return IZPI_OK;
+}
+NoiseParams noise_params(izpi_ctx* ctx) {
+  const izpi_ctx::Session& ss = ctx->session;
+  NoiseParams np{};
+  np.num_pixels = ss.num_pixels; np.done = ss.done; np.width = ss.req.width; np.height = ss.req.height;
+  np.tile_w = ss.tile_w; np.tile_h = ss.tile_h; np.sampler = ss.req.sampler; np.out_layout = ss.req.out_layout;
+  np.threshold = IZPI_NOISE_DEFAULT_THRESHOLD; np.floor = IZPI_NOISE_DEFAULT_FLOOR;
+  np.tiles = ctx->d_tiles; np.running = ctx->d_running; np.moments = ctx->d_moments;
+  return np;
+}
+
+// noise: k_noise_stats over the sums and moments; the block sums are added here, in block order.
+int session_noise(izpi_ctx* ctx, const izpi_noise_params* params, izpi_noise_stats* out) {
+  int rc = session_usable(ctx);
+  if (rc) return rc;
+  const izpi_noise_params p = params ? *params : nz::defaults();
+  if (const char* bad = nz::check_params(p)) { ctx->err = bad; return IZPI_ERR_INVALID; }
+  if ((rc = session_has_noise(ctx))) return rc;
+  const izpi_ctx::Session& ss = ctx->session;
+  hipStream_t st = ctx->stream;
+  if ((rc = session_tiles(ctx))) return rc;
+  const size_t blocks = ((size_t)ss.num_pixels + nz::BLOCK - 1) / nz::BLOCK;
+  if ((rc = grow(ctx, (void**)&ctx->d_noisepart, &ctx->noisepart_cap, 5 * blocks * sizeof(double)))) return rc;
+  NoiseParams np = noise_params(ctx);
+  np.threshold = p.threshold; np.floor = p.floor;
+  np.block_sums = ctx->d_noisepart;
+  np.block_counts = (unsigned long long*)(ctx->d_noisepart + blocks);
+  HIP_TRY(hipEventRecord(ctx->ev0, st));
+  launch_noise_stats(st, np);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(ctx->ev1, st));
+  std::vector<double> part(5 * blocks);
+  HIP_TRY(hipMemcpyAsync(part.data(), ctx->d_noisepart, part.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  float ms = 0;
+  HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+  izpi_noise_stats s{};
+  unsigned long long max_bits = 0;
+  for (size_t b = 0; b < blocks; b++) {  // (every block writes its partials: nothing to zero)
+    unsigned long long cnt[4];
+    memcpy(cnt, part.data() + blocks + 4 * b, sizeof(cnt));
+    s.pixels += cnt[0]; s.nonfinite += cnt[1]; s.above += cnt[2];
+    max_bits = std::max(max_bits, cnt[3]);
+    s.sum_error = s.sum_error + part[b];
+  }
+  s.max_error = gm::from_bits(max_bits);
+  s.device_ms = ms;
+  s.done = ss.done;
+  s.converged = nz::converged(s.pixels, s.nonfinite, s.above, s.done, p);
+  if (out) *out = s;
+  return IZPI_OK;
+}
+
+// converge: step(step_spp), then the statistic once done >= max(2, min_spp), until the frame is
+// converged or the cap is reached. `step` and `noise` are the session's own (one context or
+// the devices of a group); done() reads its samples.
+template <class Step, class Noise, class Done>
+int converge_loop(const izpi_noise_params* params, uint32_t cap, Step step, Noise noise, Done done, izpi_noise_stats* out) {
+  const izpi_noise_params p = params ? *params : nz::defaults();
+  izpi_noise_stats last{};
+  int rc = IZPI_OK;
+  while (!rc && done() < cap) {
+    if ((rc = step())) break;
+    if (done() < std::max(2u, p.min_spp)) continue;
+    if ((rc = noise(&p, &last))) break;
+    if (last.converged) break;
+  }
+  if (out) *out = last;
+  return rc;
+}
+
 // snapshot: k_resolve of the sums into device memory, then (IZPI_SNAP_CANVAS) the request's post.
 int session_snapshot(izpi_ctx* ctx, uint32_t form, double* out_dev) {
   int rc = session_usable(ctx);
   if (rc) return rc;
   const izpi_ctx::Session& ss = ctx->session;
-  if (form != IZPI_SNAP_CANVAS && form != IZPI_SNAP_DISPLAY) { ctx->err = "unknown snapshot form"; return IZPI_ERR_INVALID; }
+  if (form != IZPI_SNAP_CANVAS && form != IZPI_SNAP_DISPLAY && form != IZPI_SNAP_NOISE) { ctx->err = "unknown snapshot form"; return IZPI_ERR_INVALID; }
   if (ss.done == 0) { ctx->err = "snapshot before the session's first sample"; return IZPI_ERR_INVALID; }
+  if (form == IZPI_SNAP_NOISE && (rc = session_has_noise(ctx))) return rc;
   if (!out_dev) { ctx->err = "null output"; return IZPI_ERR_INVALID; }
   hipStream_t st = ctx->stream;
-  // (izpi_gpu_unpack_tiles may have used d_tiles since the last step)
-  if ((rc = grow(ctx, (void**)&ctx->d_tiles, &ctx->tiles_cap, ss.run_tiles.size() * sizeof(uint32_t)))) return rc;
-  HIP_TRY(hipMemcpyAsync(ctx->d_tiles, ss.run_tiles.data(), ss.run_tiles.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  if ((rc = session_tiles(ctx))) return rc;
+  if (form == IZPI_SNAP_NOISE) {  // k_noise_resolve: the standard errors, where k_resolve writes the pixels; no post
+    NoiseParams np = noise_params(ctx);
+    np.out = out_dev;
+    launch_noise_resolve(st, np);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    return IZPI_OK;
+  }
   ResolveParams rp{};
   rp.num_pixels = ss.num_pixels; rp.done = ss.done; rp.width = ss.req.width; rp.height = ss.req.height;
   rp.tile_w = ss.tile_w; rp.tile_h = ss.tile_h; rp.sampler = ss.req.sampler; rp.out_layout = ss.req.out_layout;
@@ -1014,6 +1123,13 @@ int on_every_device(izpi_multi* m, F fn) {
   for (uint32_t i = 0; i < G; i++)
     if (rcs[i]) { m->err = "device " + std::to_string(i) + ": " + m->ctx[i]->err; return rcs[i]; }
   return IZPI_OK;
+}
+
+// (true, with the message, when the group's session cannot give a noise estimate)
+bool multi_lacks_noise(izpi_multi* m) {
+  if (!m->session.noise) { m->err = "noise: the session was begun without IZPI_PROG_NOISE"; return true; }
+  if (m->session.done < 2) { m->err = "noise: needs at least 2 samples"; return true; }
+  return false;
 }
 
 bool multi_session_open(izpi_multi* m) {
@@ -1218,10 +1334,35 @@ int izpi_gpu_prepare(izpi_ctx* ctx, const izpi_render_req* req) {
   return render_impl(ctx, req, one_shot(req, true), nullptr);
 }
 
-int izpi_gpu_progressive_begin(izpi_ctx* ctx, const izpi_render_req* req, uint32_t step_spp) {
+int izpi_gpu_progressive_begin_ex(izpi_ctx* ctx, const izpi_render_req* req, uint32_t step_spp, uint32_t flags) {
   if (!ctx) return IZPI_ERR_INVALID;
   HIP_TRY(hipSetDevice(ctx->device));
-  return session_begin(ctx, req, step_spp);
+  return session_begin(ctx, req, step_spp, flags);
+}
+
+int izpi_gpu_progressive_begin(izpi_ctx* ctx, const izpi_render_req* req, uint32_t step_spp) {
+  return izpi_gpu_progressive_begin_ex(ctx, req, step_spp, 0);
+}
+
+int izpi_gpu_progressive_noise(izpi_ctx* ctx, const izpi_noise_params* p, izpi_noise_stats* out) {
+  if (!ctx) return IZPI_ERR_INVALID;
+  HIP_TRY(hipSetDevice(ctx->device));
+  return session_noise(ctx, p, out);
+}
+
+int izpi_gpu_progressive_converge(izpi_ctx* ctx, const izpi_noise_params* p, izpi_render_stats* stats, izpi_noise_stats* noise) {
+  if (!ctx) return IZPI_ERR_INVALID;
+  int rc = session_usable(ctx);
+  if (rc) return rc;
+  const izpi_noise_params q = p ? *p : nz::defaults();
+  if (const char* bad = nz::check_params(q)) { ctx->err = bad; return IZPI_ERR_INVALID; }
+  if (!ctx->session.noise) { ctx->err = "noise: the session was begun without IZPI_PROG_NOISE"; return IZPI_ERR_INVALID; }
+  HIP_TRY(hipSetDevice(ctx->device));
+  rc = converge_loop(&q, ctx->session.req.spp, [&]() { return session_step(ctx, 0, nullptr); },
+                     [&](const izpi_noise_params* np, izpi_noise_stats* ns) { return session_noise(ctx, np, ns); },
+                     [&]() { return ctx->session.done; }, noise);
+  if (stats) *stats = ctx->session.cum;
+  return rc;
 }
 
 int izpi_gpu_progressive_step(izpi_ctx* ctx, uint32_t spp, izpi_render_stats* stats) {
@@ -1565,9 +1706,14 @@ int izpi_gpu_multi_prepare(izpi_multi* m, const izpi_render_req* req) {
 // A progressive session over the devices: izpi_gpu_multi_render's share plan, one session per
 // device over its share's units (packed; a device without units has none).
 int izpi_gpu_multi_progressive_begin(izpi_multi* m, const izpi_render_req* req, uint32_t step_spp) {
+  return izpi_gpu_multi_progressive_begin_ex(m, req, step_spp, 0);
+}
+
+int izpi_gpu_multi_progressive_begin_ex(izpi_multi* m, const izpi_render_req* req, uint32_t step_spp, uint32_t flags) {
   if (!m || m->ctx.empty()) return IZPI_ERR_INVALID;
   if (m->prog_open) { m->err = "a progressive session is already open"; return IZPI_ERR_INVALID; }
   if (!req || step_spp == 0) { m->err = "progressive_begin: a request and step_spp >= 1"; return IZPI_ERR_INVALID; }
+  if (flags & ~(uint32_t)IZPI_PROG_NOISE) { m->err = "progressive_begin: unknown flags"; return IZPI_ERR_INVALID; }
   for (izpi_ctx* c : m->ctx)
     if (c->session.open) { m->err = "a context of this group has a progressive session of its own"; return IZPI_ERR_INVALID; }
   int rc = session_copy_request(m->session, req, m->err);
@@ -1591,12 +1737,13 @@ int izpi_gpu_multi_progressive_begin(izpi_multi* m, const izpi_render_req* req, 
     q.tiles = mine.data();
     q.out_layout = IZPI_OUT_PACKED;
     q.post = IZPI_POST_NONE;
-    return session_begin(c, &q, ms.step_spp);
+    return session_begin(c, &q, ms.step_spp, flags);
   });
   if (rc) {
     for (izpi_ctx* c : m->ctx) session_drop(c);
     return rc;
   }
+  ms.noise = (flags & IZPI_PROG_NOISE) != 0;
   m->shares = sh;
   m->prog_open = true;
   return IZPI_OK;
@@ -1619,8 +1766,9 @@ int izpi_gpu_multi_progressive_snapshot(izpi_multi* m, uint32_t form, double* ou
   if (!m || m->ctx.empty()) return IZPI_ERR_INVALID;
   if (!m->prog_open) { m->err = "no progressive session is open"; return IZPI_ERR_INVALID; }
   const izpi_ctx::Session& ms = m->session;
-  if (form != IZPI_SNAP_CANVAS && form != IZPI_SNAP_DISPLAY) { m->err = "unknown snapshot form"; return IZPI_ERR_INVALID; }
+  if (form != IZPI_SNAP_CANVAS && form != IZPI_SNAP_DISPLAY && form != IZPI_SNAP_NOISE) { m->err = "unknown snapshot form"; return IZPI_ERR_INVALID; }
   if (ms.done == 0) { m->err = "snapshot before the session's first sample"; return IZPI_ERR_INVALID; }
+  if (form == IZPI_SNAP_NOISE && multi_lacks_noise(m)) return IZPI_ERR_INVALID;
   izpi_ctx* root = m->ctx[0];
   const Shares& sh = m->shares;
   const size_t canvas_bytes = (size_t)ms.req.width * ms.req.height * 4 * sizeof(double);
@@ -1647,13 +1795,48 @@ int izpi_gpu_multi_progressive_snapshot(izpi_multi* m, uint32_t form, double* ou
   if (rc) return rc;
   if (hipSetDevice(root->device) != hipSuccess) { m->err = "hipSetDevice"; return IZPI_ERR_HIP; }
   izpi_render_req q = ms.req;
-  if (form != IZPI_SNAP_CANVAS) q.post = IZPI_POST_NONE;  // the display pixels are not post-processed
+  if (form != IZPI_SNAP_CANVAS) q.post = IZPI_POST_NONE;  // the display pixels and the standard errors are not post-processed
   if ((rc = assemble(root, &q, sh, root->d_out))) { m->err = root->err; return rc; }
   if (out_host && hipMemcpy(out_host, root->d_out, canvas_bytes, hipMemcpyDeviceToHost) != hipSuccess) {
     m->err = "hipMemcpy";
     return IZPI_ERR_HIP;
   }
   return IZPI_OK;
+}
+
+// The devices' statistics in one: the integers added, the largest maximum, sum_error added in
+// device order (its last bits depend on the share plan), the slowest device's time.
+int izpi_gpu_multi_progressive_noise(izpi_multi* m, const izpi_noise_params* p, izpi_noise_stats* out) {
+  if (!m || m->ctx.empty()) return IZPI_ERR_INVALID;
+  if (!m->prog_open) { m->err = "no progressive session is open"; return IZPI_ERR_INVALID; }
+  const izpi_noise_params q = p ? *p : nz::defaults();
+  if (const char* bad = nz::check_params(q)) { m->err = bad; return IZPI_ERR_INVALID; }
+  if (multi_lacks_noise(m)) return IZPI_ERR_INVALID;
+  std::vector<izpi_noise_stats> part(m->ctx.size());
+  const int rc = on_every_device(m, [&](uint32_t i, izpi_ctx* c) { return c->session.open ? session_noise(c, &q, &part[i]) : (int)IZPI_OK; });
+  if (rc) return rc;
+  izpi_noise_stats s{};
+  for (const izpi_noise_stats& d : part) {
+    s.pixels += d.pixels; s.nonfinite += d.nonfinite; s.above += d.above;
+    s.max_error = std::max(s.max_error, d.max_error);
+    s.sum_error = s.sum_error + d.sum_error;
+    s.device_ms = std::max(s.device_ms, d.device_ms);
+  }
+  s.done = m->session.done;
+  s.converged = nz::converged(s.pixels, s.nonfinite, s.above, s.done, q);
+  if (out) *out = s;
+  return IZPI_OK;
+}
+
+int izpi_gpu_multi_progressive_converge(izpi_multi* m, const izpi_noise_params* p, izpi_render_stats* stats, izpi_noise_stats* noise) {
+  if (!m || m->ctx.empty()) return IZPI_ERR_INVALID;
+  if (!m->prog_open) { m->err = "no progressive session is open"; return IZPI_ERR_INVALID; }
+  const izpi_noise_params q = p ? *p : nz::defaults();
+  if (const char* bad = nz::check_params(q)) { m->err = bad; return IZPI_ERR_INVALID; }
+  if (!m->session.noise) { m->err = "noise: the session was begun without IZPI_PROG_NOISE"; return IZPI_ERR_INVALID; }
+  return converge_loop(&q, m->session.req.spp, [&]() { return izpi_gpu_multi_progressive_step(m, 0, stats); },
+                       [&](const izpi_noise_params* np, izpi_noise_stats* ns) { return izpi_gpu_multi_progressive_noise(m, np, ns); },
+                       [&]() { return m->session.done; }, noise);
 }
 
 int izpi_gpu_multi_progressive_end(izpi_multi* m) {

@@ -8,6 +8,7 @@
 //   izpi_gpu.hip  the C ABI, the context, scene upload, the render call, multi-GPU
 //                 (render_plan.cpp: its workspace plan, plain C++);
 //   denoise.hip   k_denoise and the izpi_gpu_denoise entries (denoise.h: the arithmetic).
+//   noise.hip     k_noise_resolve, k_noise_stats: a session's noise estimate (noise.h: the arithmetic).
 // Device helpers (textures, spectra, the wavefront state, hit records, lights, materials,
 // the shading records) and the host context live here. Not part of the ABI.
 #pragma once
@@ -1480,6 +1481,21 @@ struct ResolveParams {
   double* out;
 };
 void launch_resolve(hipStream_t st, const ResolveParams& rp);
+// k_noise_resolve and k_noise_stats (noise.hip): the noise estimate of a session begun with
+// IZPI_PROG_NOISE, from its sums and second moments after `done` >= 2 samples (noise.h; DESIGN.md
+// section 3.9). Both are read only.
+struct NoiseParams {
+  uint32_t num_pixels, done, width, height, tile_w, tile_h, sampler, out_layout;
+  double threshold, floor;  // k_noise_stats
+  const uint32_t* tiles;
+  const double* running;  // [num_pixels][3]
+  const double* moments;  // [num_pixels][3]
+  double* out;            // k_noise_resolve: (se_0, se_1, se_2, 1.0) per pixel, in k_resolve's layout
+  double* block_sums;     // k_noise_stats: v[0] of each 256-pixel block, [ceil(num_pixels / 256)]
+  unsigned long long* block_counts;  // k_noise_stats: each block's pixels, nonfinite, above and the bits of its largest e, [blocks][4]
+};
+void launch_noise_resolve(hipStream_t st, const NoiseParams& np);
+void launch_noise_stats(hipStream_t st, const NoiseParams& np);
 // ================================================================ host side
 // The record sizes the workspace planner counts with (render_plan.h), against the real types.
 static_assert(sizeof(RayOD) == izpi_internal::plan_size::RAY && sizeof(PathHot) == izpi_internal::plan_size::PATH_HOT &&
@@ -1548,6 +1564,9 @@ struct izpi_ctx {
   double* d_share = nullptr; size_t share_cap = 0;    // multi-GPU: this device's packed tiles
   double* d_gather = nullptr; size_t gather_cap = 0;  // multi-GPU root: every device's packed tiles
   double* d_denoise = nullptr; size_t denoise_cap = 0;  // izpi_gpu_denoise_device's scratch canvas (denoise.hip; it only grows)
+  // a session begun with IZPI_PROG_NOISE (noise.hip; both only grow, and no workspace plan counts them):
+  double* d_moments = nullptr; size_t moments_cap = 0;  // the samples' second moments, [num_pixels][3]
+  double* d_noisepart = nullptr; size_t noisepart_cap = 0;  // k_noise_stats' block partials: [blocks] sums, then [blocks][4] counts
   uint32_t* h_count = nullptr;                        // pinned readback of d_misc (unit head, queue lengths; same stride) + scratch
   hipEvent_t ev3 = nullptr;
   hipEvent_t evb[3 * IZPI_PASS_BATCH] = {};
@@ -1584,6 +1603,7 @@ struct izpi_ctx {
     std::vector<uint32_t> tiles;  // the request's own list (may be empty: the whole frame)
     std::vector<double> bg_wl, bg_val;
     uint32_t step_spp = 0, done = 0;
+    bool noise = false;  // IZPI_PROG_NOISE: the steps fold the second moments into d_moments
     // filled by render_body: the tiles rendered, their extent and pixels
     std::vector<uint32_t> run_tiles;
     uint32_t tile_w = 0, tile_h = 0, num_pixels = 0;
@@ -1651,7 +1671,12 @@ int run_wavefront(izpi_ctx* ctx, const izpi_render_req* req, const DevScene& sc,
                   ShadeParams& sp, WaveParams& wp, AccumParams& ap, const RunInput& in, RunTimes* out);
 int prepare_wavefront(izpi_ctx* ctx, const ShadeKernels& k);
 int prepare_accumulate(izpi_ctx* ctx);
-void launch_accumulate(hipStream_t st, const AccumParams& ap);
+void launch_accumulate(hipStream_t st, const AccumParams& ap, double* moments = nullptr);
+// The moments k_accumulate folds besides the sums: those of a noise session's steps, else none
+// (the present instance runs).
+inline double* session_moments(const izpi_ctx* ctx, const SampleRange& r) {
+  return r.keep && ctx->session.noise ? ctx->d_moments : nullptr;
+}
 // preview.hip: the Normal, Albedo and WireFrame samplers (sampler/normal.go, albedo.go,
 // wireframe.go): one primary ray per sample, no path state. The request's units run in
 // batches of `slots`: k_preview_start writes the batch's camera rays into `buf` (start_path),

@@ -9,6 +9,8 @@
 //               [--sampler colour|normal|wireframe|albedo|spectral] [--ink r,g,b]
 //               [--progressive STEP [--snapshots PREFIX]]
 //               [--denoise [N] [--denoise-sigma c,n,a]]
+//               [--progressive STEP --noise-threshold T [--noise-tolerated F] [--noise-floor L]
+//                [--min-samples K] [--noise-out se.pfm]]
 //
 // --denoise [N] (--sampler colour or spectral) filters the frame with N iterations (default
 // IZPI_DENOISE_DEFAULT_ITERATIONS) of the edge-avoiding a-trous denoiser (izpi_gpu_denoise,
@@ -21,6 +23,16 @@
 // session, izpi_gpu_progressive_*) and --snapshots PREFIX writes PREFIX_<done>.pfm after each
 // step; --out / --raw get the last snapshot, byte for byte the files the same command writes
 // without --progressive.
+//
+// --noise-threshold T (with --progressive STEP) stops by the noise estimate's rule (DESIGN.md
+// section 3.9, izpi_gpu_progressive_noise): after each step from max(2, --min-samples) samples
+// on, the frame statistic is evaluated and printed on stderr as one
+//   IZPI_NOISE done= pixels= above= nonfinite= max= mean=
+// line, and the render ends when at most --noise-tolerated (a share, default 0.05) of the
+// finite pixels have a relative error above T, or at --samples. --out / --raw get the frame
+// at the samples spent, byte for byte the file of a render at --samples done; --noise-out
+// gets the per-pixel standard errors (IZPI_SNAP_NOISE) as a PFM. --min-samples (default 8)
+// guards against the underestimated variance of the first few samples.
 //
 // Defaults are the Go shim's: the GPU-built tree and the forward accumulation
 // (IZPI_ACC_FORWARD; --accumulation recursive is bit-identical to the CPU oracle).
@@ -91,6 +103,10 @@ int main(int argc, char** argv) {
   bool denoise = false;
   izpi_denoise_params dparams = {IZPI_DENOISE_DEFAULT_ITERATIONS, 0, IZPI_DENOISE_DEFAULT_SIGMA_COLOUR,
                                  IZPI_DENOISE_DEFAULT_SIGMA_NORMAL, IZPI_DENOISE_DEFAULT_SIGMA_ALBEDO};
+  bool noise = false;
+  izpi_noise_params nparams = {IZPI_NOISE_DEFAULT_THRESHOLD, IZPI_NOISE_DEFAULT_FLOOR, IZPI_NOISE_DEFAULT_TOLERATED,
+                               IZPI_NOISE_DEFAULT_MIN_SPP, 0};
+  std::string noise_out;
   double ink[3] = {0.0, 0.0, 0.0};
   bool quantized = false;
   uint32_t W = 1024, H = 1024, spp = 16, depth = 50, device = 0, gpus = 1;
@@ -126,6 +142,11 @@ int main(int argc, char** argv) {
       if (sscanf(val().c_str(), "%lf,%lf,%lf", &dparams.sigma_colour, &dparams.sigma_normal, &dparams.sigma_albedo) != 3)
         die("--denoise-sigma takes colour,normal,albedo");
     }
+    else if (a == "--noise-threshold") { noise = true; nparams.threshold = atof(val().c_str()); }
+    else if (a == "--noise-tolerated") nparams.tolerated = atof(val().c_str());
+    else if (a == "--noise-floor") nparams.floor = atof(val().c_str());
+    else if (a == "--min-samples") nparams.min_spp = (uint32_t)atoi(val().c_str());
+    else if (a == "--noise-out") noise_out = val();
     else if (a == "--ink") { if (sscanf(val().c_str(), "%lf,%lf,%lf", &ink[0], &ink[1], &ink[2]) != 3) die("--ink takes r,g,b"); }
     else die("unknown option " + a);
   }
@@ -133,6 +154,8 @@ int main(int argc, char** argv) {
   if (bvh != "gpu" && bvh != "reference") die("--bvh must be gpu or reference");
   if (acc != "forward" && acc != "recursive") die("--accumulation must be forward or recursive");
   if (!snap_prefix.empty() && !progressive) die("--snapshots needs --progressive");
+  if (noise && !progressive) die("--noise-threshold needs --progressive");
+  if (!noise_out.empty() && !noise) die("--noise-out needs --noise-threshold");
   // ---- scene file (leader.go:54-75)
   std::vector<char> text;
   if (!read_file(scene_path, text)) die("cannot read " + scene_path);
@@ -231,15 +254,36 @@ int main(int argc, char** argv) {
   req.accumulation = acc == "forward" ? IZPI_ACC_FORWARD : IZPI_ACC_RECURSIVE;
   std::vector<double> canvas((size_t)W * H * 4);
   std::vector<izpi_render_stats> stv(gpus > 1 ? gpus : 1);
+  uint32_t spent = spp;  // samples per pixel in the canvas (fewer when the noise rule stopped the render)
   auto t1 = std::chrono::steady_clock::now();
   if (progressive) {
     // the frame in steps; a snapshot after each (the last one is the frame)
     auto ok = [&](int r) { if (r) die(multi ? izpi_gpu_multi_last_error(multi) : izpi_gpu_last_error(ctx)); };
-    ok(multi ? izpi_gpu_multi_progressive_begin(multi, &req, progressive) : izpi_gpu_progressive_begin(ctx, &req, progressive));
-    for (uint32_t done = 0; done < spp;) {
+    const uint32_t flags = noise ? (uint32_t)IZPI_PROG_NOISE : 0u;
+    ok(multi ? izpi_gpu_multi_progressive_begin_ex(multi, &req, progressive, flags) : izpi_gpu_progressive_begin_ex(ctx, &req, progressive, flags));
+    bool stop = false;
+    for (uint32_t done = 0; done < spp && !stop;) {
       ok(multi ? izpi_gpu_multi_progressive_step(multi, 0, stv.data()) : izpi_gpu_progressive_step(ctx, 0, stv.data()));
       done = done + progressive < spp ? done + progressive : spp;
-      if (snap_prefix.empty() && done < spp) continue;
+      if (noise && done >= (nparams.min_spp > 2 ? nparams.min_spp : 2u)) {  // izpi_gpu_progressive_converge's rule, an evaluation at a time
+        izpi_noise_stats ns;
+        ok(multi ? izpi_gpu_multi_progressive_noise(multi, &nparams, &ns) : izpi_gpu_progressive_noise(ctx, &nparams, &ns));
+        const uint64_t fin = ns.pixels - ns.nonfinite;
+        fprintf(stderr, "IZPI_NOISE done=%u pixels=%llu above=%llu nonfinite=%llu max=%.6g mean=%.6g\n", ns.done,
+                (unsigned long long)ns.pixels, (unsigned long long)ns.above, (unsigned long long)ns.nonfinite, ns.max_error,
+                fin ? ns.sum_error / (double)fin : 0.0);
+        stop = ns.converged != 0;
+      }
+      if (stop || done == spp) {
+        spent = done;
+        if (!noise_out.empty() && done >= 2) {
+          std::vector<double> se((size_t)W * H * 4);
+          ok(multi ? izpi_gpu_multi_progressive_snapshot(multi, IZPI_SNAP_NOISE, se.data())
+                   : izpi_gpu_progressive_snapshot(ctx, IZPI_SNAP_NOISE, se.data()));
+          write_pfm(noise_out, se, W, H);
+        }
+      }
+      if (snap_prefix.empty() && done < spp && !stop) continue;
       ok(multi ? izpi_gpu_multi_progressive_snapshot(multi, IZPI_SNAP_CANVAS, canvas.data())
                : izpi_gpu_progressive_snapshot(ctx, IZPI_SNAP_CANVAS, canvas.data()));
       if (!snap_prefix.empty()) write_pfm(snap_prefix + "_" + std::to_string(done) + ".pfm", canvas, W, H);
@@ -276,8 +320,8 @@ int main(int argc, char** argv) {
   const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
   printf("{\"scene\": \"%s\", \"width\": %u, \"height\": %u, \"spp\": %u, \"bvh\": \"%s\", \"quantized\": %d, \"accumulation\": \"%s\", \"sampler\": \"%s\", \"gpus\": %u, "
          "\"setup_s\": %.3f, \"render_s\": %.4f, \"msamples_per_s\": %.2f, \"rays\": %llu, \"node_visits\": %llu}\n",
-         scene_path.c_str(), W, H, spp, bvh.c_str(), bvh == "gpu" && quantized ? 1 : 0, acc.c_str(), sampler_name.c_str(), gpus > 1 ? gpus : 1u, setup_s, secs,
-         (double)W * H * spp / secs / 1e6, (unsigned long long)st.rays, (unsigned long long)st.node_visits);
+         scene_path.c_str(), W, H, spent, bvh.c_str(), bvh == "gpu" && quantized ? 1 : 0, acc.c_str(), sampler_name.c_str(), gpus > 1 ? gpus : 1u, setup_s, secs,
+         (double)W * H * spent / secs / 1e6, (unsigned long long)st.rays, (unsigned long long)st.node_visits);
   // ---- outputs
   if (!out_raw.empty()) {
     FILE* f = fopen(out_raw.c_str(), "wb");

@@ -1,0 +1,111 @@
+// noise.hip — the noise estimate of a progressive session on the device (DESIGN.md section
+// 3.9): k_noise_resolve, the IZPI_SNAP_NOISE snapshot, and k_noise_stats, the frame statistic
+// behind izpi_gpu_progressive_noise (include/izpi_gpu.h). The arithmetic is noise.h's, shared
+// with the host twin (noise_host.cpp), so both give the same bits. The second moments both
+// read are folded by k_accumulate's moments instance (wavefront.hip). A translation unit of
+// its own, so the other units compile what they compiled before.
+#include "izpi_kern.h"
+#include "noise.h"
+
+namespace {
+
+// Pixel p's sums and moments (48 B).
+__device__ __forceinline__ void load_pixel(const NoiseParams& np, uint32_t p, double s[3], double m2[3]) {
+  for (int c = 0; c < 3; c++) {
+    s[c] = np.running[3 * (size_t)p + c];
+    m2[c] = np.moments[3 * (size_t)p + c];
+  }
+}
+
+// Pixel p of the packed order sits at (x, y) of the frame (k_resolve's index rule).
+__device__ __forceinline__ void pixel_xy(const NoiseParams& np, uint32_t p, uint32_t* x, uint32_t* y) {
+  const uint32_t tile_px = np.tile_w * np.tile_h;
+  const uint32_t tile = p / tile_px, in_tile = p % tile_px;
+  *x = np.tiles[4 * tile] + in_tile % np.tile_w;
+  *y = np.tiles[4 * tile + 1] + in_tile / np.tile_w;
+}
+
+}  // namespace
+
+// One thread per pixel in packed order: 48 B of sums and moments in, 32 B out; HBM-streaming.
+// Writes (se_0, se_1, se_2, 1.0) where k_resolve writes the pixel.
+__global__ void __launch_bounds__(256) k_noise_resolve(const NoiseParams np) {
+  const uint32_t p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= np.num_pixels) return;
+  double s[3], m2[3], se[3], e;
+  load_pixel(np, p, s, m2);
+  nz::pixel(s, m2, np.done, np.sampler == IZPI_SAMPLER_SPECTRAL, np.floor, se, &e);
+  double* o;
+  if (np.out_layout == IZPI_OUT_PACKED) {
+    o = np.out + (size_t)p * 4;
+  } else {  // canvas.Set(x, ny - y), row ny is dropped (A9)
+    uint32_t x, y;
+    pixel_xy(np, p, &x, &y);
+    const uint32_t row = np.height - y;
+    if (row >= np.height) return;
+    o = np.out + ((size_t)row * np.width + x) * 4;
+  }
+  o[0] = se[0]; o[1] = se[1]; o[2] = se[2]; o[3] = 1.0;
+}
+
+// The frame statistic: one thread per pixel in packed order, blocks of nz::BLOCK = 256 = four
+// waves. Every wave counts its counted, non-finite and above-threshold pixels by ballot and
+// takes the maximum of its finite e on the bit pattern (non-negative doubles order as their
+// bits); the four waves' figures meet in LDS and go out as the block's partials, which the
+// host adds (one atomic per wave on four shared words measured 0.44 ms per 1024 x 1024
+// evaluation, 27 times the kernel's bytes' worth: profiles/r13a/). sum_error's tree
+// (izpi_gpu.h) is taken literally: strides 128 and 64 across the four waves through LDS,
+// strides 32 ... 1 within the first wave by __shfl_down, and v[0] goes to block_sums, which the
+// host adds in block order. No thread leaves before the barriers.
+__global__ void __launch_bounds__(nz::BLOCK) k_noise_stats(const NoiseParams np) {
+  __shared__ double v[nz::BLOCK];
+  __shared__ unsigned long long part[nz::BLOCK / 64][4];
+  const uint32_t t = threadIdx.x;
+  const uint32_t p = blockIdx.x * nz::BLOCK + t;
+  bool counted = false, fin = false;
+  double e = 0.0;
+  if (p < np.num_pixels) {
+    uint32_t x, y;
+    pixel_xy(np, p, &x, &y);
+    counted = y >= 1;
+    double s[3], m2[3], se[3];
+    load_pixel(np, p, s, m2);
+    fin = nz::pixel(s, m2, np.done, np.sampler == IZPI_SAMPLER_SPECTRAL, np.floor, se, &e);
+  }
+  const bool good = counted && fin;
+  const double mine = good ? e : 0.0;
+  const unsigned long long n_counted = __popcll(__ballot(counted));
+  const unsigned long long n_bad = __popcll(__ballot(counted && !fin));
+  const unsigned long long n_above = __popcll(__ballot(good && e > np.threshold));
+  // the wave's largest e (every term is >= +0.0)
+  double mx = mine;
+  for (int off = 32; off; off >>= 1) {
+    const double o = __shfl_down(mx, off);
+    mx = o > mx ? o : mx;
+  }
+  if ((t & 63u) == 0) {
+    unsigned long long* w = part[t >> 6];
+    w[0] = n_counted; w[1] = n_bad; w[2] = n_above; w[3] = gm::bits(mx);
+  }
+  v[t] = mine;
+  __syncthreads();
+  if (t < 4) {  // the block's pixels, nonfinite, above (sums) and the bits of its largest e (maximum)
+    unsigned long long a = part[0][t];
+    for (uint32_t w = 1; w < nz::BLOCK / 64; w++) a = t < 3 ? a + part[w][t] : (part[w][t] > a ? part[w][t] : a);
+    np.block_counts[4 * (size_t)blockIdx.x + t] = a;
+  }
+  if (t < 128) v[t] = v[t] + v[t + 128];
+  __syncthreads();
+  if (t < 64) {
+    double a = v[t] + v[t + 64];
+    for (int stride = 32; stride; stride >>= 1) a = a + __shfl_down(a, stride);
+    if (t == 0) np.block_sums[blockIdx.x] = a;
+  }
+}
+
+void launch_noise_resolve(hipStream_t st, const NoiseParams& np) {
+  hipLaunchKernelGGL(k_noise_resolve, dim3((np.num_pixels + 255) / 256), dim3(256), 0, st, np);
+}
+void launch_noise_stats(hipStream_t st, const NoiseParams& np) {
+  hipLaunchKernelGGL(k_noise_stats, dim3((np.num_pixels + nz::BLOCK - 1) / nz::BLOCK), dim3(nz::BLOCK), 0, st, np);
+}

@@ -165,7 +165,7 @@ int run_preview(izpi_ctx* ctx, const izpi_render_req* req, const DevScene& sc, c
     ap.chunk_spp = cs;
     ap.raw_spectral = 0;
     ap.last = (!sr.keep && s0 + cs >= sr.end) ? 1u : 0u;
-    launch_accumulate(st, ap);
+    launch_accumulate(st, ap, session_moments(ctx, sr));
     HIP_TRY(hipGetLastError());
   }
   return IZPI_OK;

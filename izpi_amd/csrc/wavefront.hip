@@ -5,6 +5,9 @@
 // kernels of the loop that depend on no instance: the forward refill's plans, the overflow
 // pool's rings, the ordered per-pixel sums (k_accumulate, which the preview samplers share).
 #include "izpi_kern.h"
+#include "noise.h"
+
+#include <type_traits>
 
 // Forward mode's refill (k_shade<..., FWD = true>): after a shading pass, the entries its
 // finished paths freed take the next units, as one run of camera rays appended behind the
@@ -50,10 +53,22 @@ static __global__ void k_pool_init(uint32_t* ring, uint32_t n, uint32_t per_ring
   }
 }
 
-static __global__ void __launch_bounds__(256) k_accumulate(const AccumParams ap) {
+// k_accumulate in its two instances, chosen by the parameter type: P = AccumParams is the
+// kernel every render runs; P = AccumMoments (AccumParams and one more pointer: AccumParams
+// itself stays as it is) is the moments instance of a session begun with IZPI_PROG_NOISE, which
+// also folds each sample's squares into `moments` ([num_pixels][3], DESIGN.md section 3.9:
+// nz::fold) in the same pass over the same bytes. The sums' additions are the same in both.
+struct AccumMoments : AccumParams {
+  double* moments;
+};
+template <class P>
+static __global__ void __launch_bounds__(256) k_accumulate(const P ap) {
+  constexpr bool M2 = !std::is_same<P, AccumParams>::value;
   const uint32_t p = blockIdx.x * 256 + threadIdx.x;
   if (p >= ap.num_pixels) return;
   double c0 = ap.running[3 * (size_t)p], c1 = ap.running[3 * (size_t)p + 1], c2 = ap.running[3 * (size_t)p + 2];
+  double q0 = 0, q1 = 0, q2 = 0;
+  if constexpr (M2) { q0 = ap.moments[3 * (size_t)p]; q1 = ap.moments[3 * (size_t)p + 1]; q2 = ap.moments[3 * (size_t)p + 2]; }
   const double* s = ap.samples + (size_t)p * ap.chunk_spp * SMP_D;
   uint32_t k = 0;
   // one sample into the sums (rgb.go:36 col += ..., render/spectral.go:92-96 sum += ...);
@@ -63,8 +78,10 @@ static __global__ void __launch_bounds__(256) k_accumulate(const AccumParams ap)
       double x, y, z;
       spectral_weigh(a, b, c, x, y, z);
       c0 = c0 + x; c1 = c1 + y; c2 = c2 + z;
+      if constexpr (M2) nz::fold(x, y, z, q0, q1, q2);
     } else {
       c0 = c0 + a; c1 = c1 + b; c2 = c2 + c;
+      if constexpr (M2) nz::fold(a, b, c, q0, q1, q2);
     }
   };
   if ( (ap.chunk_spp & 3u) == 0 && blockIdx.x * 256 + 256 <= ap.num_pixels) {
@@ -111,6 +128,7 @@ static __global__ void __launch_bounds__(256) k_accumulate(const AccumParams ap)
   for (; k < ap.chunk_spp; k++) add(s[3 * k], s[3 * k + 1], s[3 * k + 2]);  // sample order, as rgb.go:36
   if (!ap.last) {
     ap.running[3 * (size_t)p] = c0; ap.running[3 * (size_t)p + 1] = c1; ap.running[3 * (size_t)p + 2] = c2;
+    if constexpr (M2) { ap.moments[3 * (size_t)p] = q0; ap.moments[3 * (size_t)p + 1] = q1; ap.moments[3 * (size_t)p + 2] = q2; }
     return;
   }
   double r0, r1, r2;
@@ -136,12 +154,20 @@ static __global__ void __launch_bounds__(256) k_accumulate(const AccumParams ap)
   }
 }
 
-void launch_accumulate(hipStream_t st, const AccumParams& ap) {
-  hipLaunchKernelGGL(k_accumulate, dim3((ap.num_pixels + 255) / 256), dim3(256), 0, st, ap);
+void launch_accumulate(hipStream_t st, const AccumParams& ap, double* moments) {
+  const dim3 grid((ap.num_pixels + 255) / 256);
+  if (moments) {
+    AccumMoments am;
+    static_cast<AccumParams&>(am) = ap;
+    am.moments = moments;
+    hipLaunchKernelGGL(k_accumulate<AccumMoments>, grid, dim3(256), 0, st, am);
+  } else {
+    hipLaunchKernelGGL(k_accumulate<AccumParams>, grid, dim3(256), 0, st, ap);
+  }
 }
 int prepare_accumulate(izpi_ctx* ctx) {
   int blocks = 0;
-  return resident_blocks(ctx, k_accumulate, &blocks);
+  return resident_blocks(ctx, k_accumulate<AccumParams>, &blocks);
 }
 
 // The instance rule: the smallest material set that holds the scene's material kinds; the
@@ -323,7 +349,7 @@ int run_wavefront(izpi_ctx* ctx, const izpi_render_req* req, const DevScene& sc,
     ap.raw_spectral = k.fwd && k.sampler == IZPI_SAMPLER_SPECTRAL ? 1u : 0u;
     ap.last = (!sr.keep && s0 + cs >= sr.end) ? 1u : 0u;
     ctx->prog_done.store((uint64_t)(s0 + cs) * num_pixels, std::memory_order_relaxed);
-    launch_accumulate(st, ap);
+    launch_accumulate(st, ap, session_moments(ctx, sr));
     HIP_TRY(hipGetLastError());
   }
   return IZPI_OK;

@@ -120,6 +120,29 @@ def denoise_device(ctx, colour_ptr, normal_ptr, albedo_ptr, out_ptr, width, heig
     return ms.value
 
 
+def host_noise(sums, moment2, done, sampler=N.SAMPLER_COLOUR, counted=None, params=None):
+    """izpi_host_noise: the host twin of a progressive session's noise estimate (DESIGN.md
+    3.9) over (n, 3) float64 sums and second moments after `done` samples, in packed pixel
+    order; counted: a (n,) mask of the pixels the statistic counts (None: all); params an
+    N.NoiseParams (None = the library's defaults). Returns (se (n, 4), stats dict). Needs no GPU."""
+    sums = np.ascontiguousarray(sums, np.float64).reshape(-1, 3)
+    moment2 = np.ascontiguousarray(moment2, np.float64).reshape(-1, 3)
+    if sums.shape != moment2.shape:
+        raise ValueError("sums and moment2 are both (n, 3)")
+    if counted is not None:
+        counted = np.ascontiguousarray(counted, np.uint8).reshape(-1)
+        if len(counted) != len(sums):
+            raise ValueError("counted has one entry per pixel")
+    se = np.zeros((len(sums), 4), np.float64)
+    st = N.NoiseStats()
+    L = N.lib()
+    rc = L.izpi_host_noise(_ptr(sums), _ptr(moment2), _ptr(counted), len(sums), int(done), int(sampler),
+                           None if params is None else C.byref(params), _ptr(se), C.byref(st))
+    if rc != 0:
+        raise RuntimeError("izpi_host_noise failed (status %d): %s" % (rc, L.izpi_host_last_error().decode()))
+    return se, st.as_dict()
+
+
 def make_request(width, height, spp, max_depth, sampler, background, seed, exposure, bg_spd=None, tiles=None,
                  layout=N.OUT_CANVAS, post=N.POST_NONE, tuning=None, accumulation=N.ACC_RECURSIVE, ink=(0.0, 0.0, 0.0)):
     """izpi_render_req for Render (the arrays it points to are kept alive on `req._keep`).
@@ -175,9 +198,14 @@ class ProgressiveSession:
     the block (or ``close()``) ends the session, which is also how a render is cancelled.
 
     ``done`` / ``total``: samples per pixel rendered so far, and the session's cap.
-    ``stats``: cumulative since the session began (a list per device for a multi-GPU one)."""
+    ``stats``: cumulative since the session began (a list per device for a multi-GPU one).
 
-    def __init__(self, owner, req, step_spp):
+    ``noise=True`` (IZPI_PROG_NOISE) also keeps the samples' second moments: ``noise()`` is
+    the frame's noise statistic, ``snapshot(N.SNAP_NOISE)`` the per-pixel standard errors and
+    ``converge()`` steps until the stop rule holds. The images and counters
+    are those of a session without it."""
+
+    def __init__(self, owner, req, step_spp, noise=False):
         self._owner = owner
         self._multi = isinstance(owner, MultiGPURenderer)
         self._handle = owner.m if self._multi else owner.ctx
@@ -188,7 +216,11 @@ class ProgressiveSession:
         self.done = 0
         self.stats = None
         self._open = False
-        self._call("begin", C.byref(req), self.step_spp)
+        self.noise_stats = None
+        if noise:
+            self._call("begin_ex", C.byref(req), self.step_spp, N.PROG_NOISE)
+        else:
+            self._call("begin", C.byref(req), self.step_spp)
         self._open = True
 
     def _call(self, what, *args):
@@ -221,6 +253,40 @@ class ProgressiveSession:
                 out = np.zeros((self._req.height, self._req.width, 4), np.float64)
         self._call("snapshot", int(form), out.ctypes.data_as(C.c_void_p))
         return out
+
+    @staticmethod
+    def _noise_params(params, kw):
+        if params is not None and kw:
+            raise ValueError("give an N.NoiseParams or keyword fields, not both")
+        return N.noise_params(**kw) if kw else params
+
+    def noise(self, params=None, **kw):
+        """izpi_gpu_progressive_noise: the frame's noise statistic after `done` >= 2 samples, as
+        a dict (pixels, nonfinite, above, max_error, sum_error, device_ms, done, converged).
+        threshold=, floor=, tolerated=, min_spp= (or an N.NoiseParams) override the defaults."""
+        p = self._noise_params(params, kw)
+        st = N.NoiseStats()
+        self._call("noise", None if p is None else C.byref(p), C.byref(st))
+        self.noise_stats = st.as_dict()
+        return self.noise_stats
+
+    def converge(self, params=None, **kw):
+        """izpi_gpu_progressive_converge: step(step_spp) and, from max(2, min_spp) samples on,
+        noise(), until the frame is converged or `done` reaches the cap. Returns the last
+        statistic (None when none was evaluated); `done` and `stats` are updated."""
+        p = self._noise_params(params, kw)
+        G = len(self._owner.devices) if self._multi else 1
+        st = (N.RenderStats * G)()
+        ns = N.NoiseStats()
+        before = self.done
+        self._call("converge", None if p is None else C.byref(p), st, C.byref(ns))
+        d, t = self._owner.progress()  # (pixels * done, pixels * cap)
+        self.done = d * self.total // t if t else self.done
+        if self.done != before:
+            self.stats = [st[i].as_dict() for i in range(G)] if self._multi else st[0].as_dict()
+            self._owner.stats = self.stats
+        self.noise_stats = ns.as_dict() if ns.done else None
+        return self.noise_stats
 
     def snapshot_device(self, out_ptr, form=N.SNAP_CANVAS):
         """snapshot() into device memory at `out_ptr` (single-GPU sessions)."""
@@ -353,11 +419,22 @@ class GPURenderer:
         req = self.request(tiles, layout, None, post)
         _check(N.lib().izpi_gpu_prepare(self.ctx, C.byref(req)), self.ctx, "izpi_gpu_prepare")
 
-    def progressive(self, step_spp, total=None, tiles=None, layout=N.OUT_CANVAS, post=N.POST_NONE):
+    def progressive(self, step_spp, total=None, tiles=None, layout=N.OUT_CANVAS, post=N.POST_NONE, noise=False):
         """Begin a progressive render of up to `total` samples per pixel (None: this
         renderer's spp) with a workspace sized for steps of `step_spp`: a ProgressiveSession.
-        render(), prepare() and a scene upload are refused until it is closed."""
-        return ProgressiveSession(self, self.request(tiles, layout, total, post), step_spp)
+        render(), prepare() and a scene upload are refused until it is closed. noise=True keeps
+        the second moments the session's noise estimate needs (24 B per pixel more)."""
+        return ProgressiveSession(self, self.request(tiles, layout, total, post), step_spp, noise)
+
+    def render_until(self, threshold, step_spp, max_spp=None, **params):
+        """Render in steps of `step_spp` until the stop rule holds at `threshold` (the other
+        izpi_noise_params as keywords: floor, tolerated, min_spp) or `max_spp` samples (None:
+        this renderer's spp) are spent. Returns (canvas, stats): the canvas is render()'s at
+        spp = stats["done"], the samples spent; stats is the last noise statistic (None when
+        max_spp came before the first evaluation: the canvas then holds max_spp samples)."""
+        with self.progressive(step_spp, total=max_spp, noise=True) as s:
+            stats = s.converge(threshold=threshold, **params)
+            return s.snapshot(), stats
 
     def progress(self):
         """(samples finished, samples of the request) of the render running on this context,
@@ -564,12 +641,12 @@ class MultiGPURenderer:
         self.stats = [st[i].as_dict() for i in range(G)]
         return canvas if to_host else None
 
-    def progressive(self, step_spp, total=None, tiles=None, layout=N.OUT_CANVAS, post=N.POST_NONE):
+    def progressive(self, step_spp, total=None, tiles=None, layout=N.OUT_CANVAS, post=N.POST_NONE, noise=False):
         """GPURenderer.progressive over all devices: each holds a session over its share."""
         req = make_request(self.width, self.height, self.spp if total is None else int(total), self.max_depth,
                            self.sampler, self.background, self.seed, self.exposure, self._bg, tiles, layout, post,
                            self.tuning, self.accumulation, self.ink)
-        return ProgressiveSession(self, req, step_spp)
+        return ProgressiveSession(self, req, step_spp, noise)
 
     def progress(self):
         """(samples finished, samples of the request) summed over the devices (izpi_gpu_multi_progress)."""
