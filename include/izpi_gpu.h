@@ -145,8 +145,10 @@ enum {
   IZPI_TUNE_NO_PLACE_PICK = 512,  /* ignored since ABI 3 (the record arrays' page pick of ABI 2 is gone) */
   IZPI_TUNE_NO_QNODES = 1024,     /* a quantised scene (IZPI_SCENE_QUANTIZED_BVH): k_trace2 reads the decoded 128-B nodes
                                      instead of the 64-B quantised ones (the same boxes) */
-  IZPI_TUNE_NO_SHADE_STAGE = 2048 /* forward Colour renders: k_shade reserves its output entries every block-iteration
+  IZPI_TUNE_NO_SHADE_STAGE = 2048,/* forward Colour renders: k_shade reserves its output entries every block-iteration
                                      instead of every other one with the first's entries staged in LDS */
+  IZPI_TUNE_WIDE_ADDR = 4096      /* k_trace2 forms the 64-bit record addresses of a scene whose arrays pass 4 GiB,
+                                     not 32-bit offsets from a scalar base */
 };
 
 typedef struct izpi_render_req {

@@ -42,6 +42,8 @@ struct DevScene {
   uint32_t lds_bytes;           // per render (render_body): k_shade / k_tail's dynamic LDS arena (lds_off)
   uint32_t time_free;           // no sphere moves: traversal needs no ray times (upload)
   uint32_t quantized;           // IZPI_SCENE_QUANTIZED_BVH: `inner` holds the decoded boxes of `innerq`
+  uint32_t addr32;              // inner, innerq and leaves are one block under 4 GiB, as are prims (trace_addr32):
+                                // k_trace2 addresses their records by 32-bit byte offsets (fills the struct's tail padding)
 #ifdef IZPI_SHADOW
   // measurement builds only (byte breakdown): copies of the traversal arrays that
   // k_trace2 reads beside the real ones, so a class's bytes past L2 show as extra FETCH_SIZE

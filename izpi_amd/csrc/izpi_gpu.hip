@@ -11,6 +11,9 @@
 using izpi_internal::Double4;
 using izpi_internal::pack_scene;
 using izpi_internal::PackedScene;
+using izpi_internal::trace_addr32;
+using izpi_internal::trace_layout;
+using izpi_internal::TraceLayout;
 using izpi_internal::PlanCache;
 using izpi_internal::PlanInput;
 using izpi_internal::SideLayout;
@@ -668,8 +671,8 @@ int render_body(izpi_ctx* ctx, const izpi_render_req* req, const RenderCall& cal
   const double t_tiles = host_ms();
   if ((rc = make_tracer(ctx, tu, !ctx->sc.tri_only || ctx->any_uv, &tr))) return rc;
   if (pass_log)  // diagnostics: the k_trace2 instance this render runs
-    fprintf(stderr, "IZPI_TRACE_INSTANCE dist=%d tri=%d lds_bvh=%d ray_lds=%d q=%d\n", (int)tr.p2, (int)tr.tri, (int)tr.lds_bvh,
-            (int)tr.ray_lds, (int)tr.qnodes);
+    fprintf(stderr, "IZPI_TRACE_INSTANCE dist=%d tri=%d lds_bvh=%d ray_lds=%d q=%d\nIZPI_TRACE_ADDR a32=%d ring=%d\n", (int)tr.p2, (int)tr.tri,
+            (int)tr.lds_bvh, (int)tr.ray_lds, (int)tr.qnodes, (int)(tr.a32 && !tr.lds_bvh), trace_ring(tr));
   const double t_tracer = host_ms();
   // Plan: the family's cached plan when the request has its shape, else from the free memory.
   PlanCache& cache = ctx->plans[rs.preview];
@@ -762,6 +765,12 @@ int render_body(izpi_ctx* ctx, const izpi_render_req* req, const RenderCall& cal
 #endif
 #ifdef IZPI_SHADOW
   fprintf(stderr, "IZPI_SHADOW spill_stores %llu spill_loads %llu (entries)\n", cnt[CNT_CLK_REFILL], cnt[CNT_CLK_NODE]);
+#endif
+#ifdef IZPI_TRACE_ICOUNT
+  fprintf(stderr, "IZPI_TRACE_ICOUNT {\"iterations\": %llu, \"idle\": %llu, \"dequeue\": %llu, \"refill\": %llu, \"prim\": %llu, \"node_fast\": %llu, "
+          "\"node_twin\": %llu, \"spill\": %llu, \"readback\": %llu, \"pop\": %llu, \"finish\": %llu, \"waves\": %llu}\n",
+          cnt[CNT_IC_ITER], cnt[CNT_IC_IDLE], cnt[CNT_IC_DEQUEUE], cnt[CNT_IC_REFILL], cnt[CNT_PSTEP], cnt[CNT_NSTEP] - cnt[CNT_IC_TWIN], cnt[CNT_IC_TWIN],
+          cnt[CNT_IC_SPILL], cnt[CNT_IC_READBACK], cnt[CNT_IC_POP], cnt[CNT_IC_FINISH], cnt[CNT_IC_WAVES]);
 #endif
 #ifdef IZPI_TRACE_CLOCKS
   fprintf(stderr, "IZPI_TRACE_CLOCKS refill %llu node %llu prim %llu advance %llu (wave cycles)\n", cnt[CNT_CLK_REFILL],
@@ -1160,9 +1169,20 @@ int upload_packed(izpi_ctx* ctx, const izpi_scene_desc* d, const PackedScene& ps
   GInner* di; GInnerQ* dq; GLeaf* dl; GPrim* dp; GShade* dsh; GTriVerts* dtv; GTriTex* dtt; GLight* dlt;
   izpi_material* dm; Double4* dmc; MatTex* dmt; izpi_texture* dtx;
   double *dtex, *dswl, *dsv;
-  UP(ps.inner.data(), ps.inner.size(), &di);
-  UP(ps.innerq.data(), ps.innerq.size(), &dq);
-  UP(ps.leaves.data(), ps.leaves.size(), &dl);
+  {  // the node block: inner, innerq and leaves in one allocation (trace_layout), so that k_trace2
+     // reaches a node step's records from one base. scene_allocs holds the block's base alone
+     // (= di: `inner` is never empty); dq and dl point into the block and are never freed on
+     // their own. (UP with no host array only allocates: the three parts are copied below.)
+    const TraceLayout tl = trace_layout(ps.inner.size(), ps.innerq.size(), ps.leaves.size());
+    char* nb;
+    UP((const char*)nullptr, tl.bytes, &nb);
+    di = reinterpret_cast<GInner*>(nb);
+    dq = ps.innerq.empty() ? nullptr : reinterpret_cast<GInnerQ*>(nb + tl.innerq_at);
+    dl = reinterpret_cast<GLeaf*>(nb + tl.leaves_at);
+    HIP_TRY(hipMemcpy(di, ps.inner.data(), ps.inner.size() * sizeof(GInner), hipMemcpyHostToDevice));
+    if (dq) HIP_TRY(hipMemcpy(dq, ps.innerq.data(), ps.innerq.size() * sizeof(GInnerQ), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dl, ps.leaves.data(), ps.leaves.size() * sizeof(GLeaf), hipMemcpyHostToDevice));
+  }
   UP(ps.prims.data(), ps.prims.size(), &dp);
   UP(ps.shade.data(), ps.shade.size(), &dsh);
   UP(ps.triverts.data(), ps.triverts.size(), &dtv);
@@ -1190,6 +1210,7 @@ int upload_packed(izpi_ctx* ctx, const izpi_scene_desc* d, const PackedScene& ps
   sc.root = ps.root; sc.num_inner = ps.num_inner; sc.num_prims = d->num_prims; sc.num_lights = d->num_lights;
   sc.quantized = ps.quantized; sc.leaf_shortcut = ps.leaf_shortcut; sc.nan_free_bounds = ps.nan_free_bounds;
   sc.tri_only = ps.tri_only; sc.time_free = ps.time_free; sc.no_pathlen = ps.no_pathlen;
+  sc.addr32 = trace_addr32(ps.inner.size(), ps.innerq.size(), ps.leaves.size(), ps.prims.size());
   sc.cam = d->camera;
   ctx->d_triverts = dtv;
   ctx->mat_ok_rgb = ps.mat_ok_rgb; ctx->mat_ok_spectral = ps.mat_ok_spectral;

@@ -96,6 +96,18 @@ enum { CNT_RAYS = 0, CNT_NODES, CNT_TRI, CNT_SPH, CNT_LTRI, CNT_LSPH, CNT_NSTEP,
        CNT_SCLK_ITEM, CNT_SCLK_REFILL, CNT_SCLK_PUSH, CNT_PARK, CNT_SCLK_MAT, CNT_SCLK_FIN, CNT_SCLK_MIX, CNT_SCLK_LPDF,
        CNT_SCLK_ENTRY, CNT_SCLK_TEX, CNT_SCLK_RB1, CNT_SCLK_RATOM, CNT_SCLK_RB2,
        CNT_N };  // SCLK_*: -DIZPI_SHADE_CLOCKS builds only  // CLK_*: -DIZPI_TRACE_CLOCKS builds only
+#ifdef IZPI_TRACE_ICOUNT
+// -DIZPI_TRACE_ICOUNT builds only: k_trace2's per-path trip counts, in the rows of the clock
+// counters (which such a build does not write), so that the frame counters' layout stays.
+// The report (render_body) takes the primitive steps and the node steps from CNT_PSTEP and
+// CNT_NSTEP: those must stay what they are, one count per wave and step, added by lane 0.
+enum { CNT_IC_ITER = CNT_CLK_REFILL, CNT_IC_DEQUEUE = CNT_CLK_NODE, CNT_IC_REFILL = CNT_CLK_PRIM, CNT_IC_TWIN = CNT_CLK_ADV,
+       CNT_IC_SPILL = CNT_SCLK_ITEM, CNT_IC_READBACK = CNT_SCLK_REFILL, CNT_IC_POP = CNT_SCLK_PUSH, CNT_IC_FINISH = CNT_SCLK_MAT,
+       CNT_IC_WAVES = CNT_SCLK_FIN, CNT_IC_IDLE = CNT_SCLK_MIX };
+#if defined(IZPI_TRACE_CLOCKS) || defined(IZPI_SHADE_CLOCKS) || defined(IZPI_SHADOW)
+#error "IZPI_TRACE_ICOUNT shares counter rows with the clock and shadow builds"
+#endif
+#endif
 
 // Frame counters without atomics: a render's kernels add their per-wave counts to the
 // wave's own row of `cpart` ([rows][CNT_N], rows = 4 x the largest grid, zeroed per frame)
@@ -1641,6 +1653,7 @@ struct Tracer {
   bool lds_bvh = false;  // LB
   bool ray_lds = false;  // RL
   bool qnodes = false;   // Q
+  bool a32 = false;      // A32 (the BVH-in-LDS instances read no record from global memory: compiled without)
   // queue entries per dequeue and idle lanes per refill, measured on C3: chunk 128 / refill
   // 16 -> 211 ms of k_trace2 per frame, 512 / 24 -> 201, 1024 -> 207, 2048 -> 216, 64 -> 303
   uint32_t prim_w = 32, tchunk = 512, refill_min = 24;
@@ -1656,6 +1669,7 @@ const izpi_render_tuning kDefaultTuning{};
 // launch it for one pass.
 int make_tracer(izpi_ctx* ctx, const izpi_render_tuning& tu, bool need_uv, Tracer* t);
 void launch_trace(izpi_ctx* ctx, const DevScene& sc, const Tracer& t, const WaveParams& wp, hipStream_t st, int32_t* spill);
+int trace_ring(const Tracer& t);  // entries of the instance's LDS stack ring (deeper stacks spill)
 // What a run of the chunk loops (run_wavefront, run_preview) is given: the pixels of the request's
 // tiles, the samples per pixel and chunk, the overflow record blocks (the path samplers), the
 // sample range; and what it reports: the device times of its passes and their number.

@@ -45,6 +45,24 @@ struct PackedScene {
 // Validate and pack *d. IZPI_OK, or the status with its text in *err; *out is then unspecified.
 int pack_scene(const izpi_scene_desc* d, PackedScene* out, std::string* err);
 
+// The node block of an uploaded scene: the inner nodes at its start, then their quantised form
+// (if any), then the leaf records, in one device allocation (byte offsets; counts of records).
+struct TraceLayout { uint64_t innerq_at, leaves_at, bytes; };
+inline TraceLayout trace_layout(uint64_t n_inner, uint64_t n_innerq, uint64_t n_leaves) {
+  TraceLayout t;
+  t.innerq_at = n_inner * sizeof(izd::GInner);
+  t.leaves_at = t.innerq_at + n_innerq * sizeof(izd::GInnerQ);
+  t.bytes = t.leaves_at + n_leaves * sizeof(izd::GLeaf);
+  return t;
+}
+// DevScene::addr32: every record of the node block starts below 4 GiB from the block's base, and
+// every primitive record below 4 GiB from the first, so k_trace2 may address them with unsigned
+// 32-bit byte offsets (a load's immediate offset within a record is added 64 bits wide).
+inline bool trace_addr32(uint64_t n_inner, uint64_t n_innerq, uint64_t n_leaves, uint64_t n_prims) {
+  const uint64_t lim = 1ull << 32;
+  return trace_layout(n_inner, n_innerq, n_leaves).bytes <= lim && n_prims * sizeof(izd::GPrim) <= lim;
+}
+
 // Upper bound on the traversal stack (bvh4.go:71-73): along any root-to-leaf path a node
 // pushes at most (valid children - 1) entries that stay below its subtree. One backward
 // pass, so children must follow their parents (pre-order does): false when a child's index

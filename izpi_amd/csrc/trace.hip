@@ -27,6 +27,11 @@
 // Q: the inner nodes are read in their quantised 64-B form (DevScene::innerq, GInnerQ) and
 // decoded into the same f32 boxes the 128-B records of a quantised scene hold; the slab test
 // and everything after it are unchanged.
+// A32: the node block (inner nodes, their quantised form, leaf records: one allocation) and the
+// primitive records each span less than 4 GiB (DevScene::addr32), so a record's address is a
+// scalar base plus one unsigned 32-bit byte offset per lane (the `saddr` form of global_load)
+// instead of a sign extension, a 64-bit shift and a 64-bit add per lane, formed once for leaf
+// and inner lanes alike inside exec-masked regions. Larger scenes keep the 64-bit addresses.
 constexpr uint32_t BVH_LDS_BYTES = 4096;
 // This lane's bit of a wave mask, as a condition (the mask becomes the select's lane mask).
 __device__ __forceinline__ bool lane_of(uint64_t mask) { return __builtin_amdgcn_inverse_ballot_w64(mask); }
@@ -35,7 +40,7 @@ __device__ __forceinline__ bool lane_of(uint64_t mask) { return __builtin_amdgcn
 __device__ __forceinline__ uint32_t lanes_below(uint64_t mask) {
   return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
 }
-template <int S, int WPE, bool DIST, bool TRI, bool LB, bool RL, bool Q>
+template <int S, int WPE, bool DIST, bool TRI, bool LB, bool RL, bool Q, bool A32>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) k_trace2(const DevScene sc, const WaveParams wp, unsigned long long* counters,
                                                 uint32_t* err, int32_t* spill, uint32_t spill_stride, uint32_t prim_w,
                                                 uint32_t tchunk, uint32_t refill_min) {
@@ -43,6 +48,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
   static_assert(!LB || DIST, "the LDS-resident BVH instance runs the distributed leaf tests");
   static_assert(!RL || (DIST && (TRI || LB)), "the LDS-resident ray instances: triangle-only global BVH, or the BVH in LDS");
   static_assert(!Q || !LB, "the quantised nodes are read from global memory");
+  static_assert(!A32 || !LB, "the 32-bit offsets address records in global memory");
   // (u, v) of the accepted hit: kept in lds_uv until the ray finishes (UVL), stored to the
   // hit record at acceptance (UVS: the BVH-in-LDS ray instance, whose steps issue no global
   // loads for the store to hold up), or not kept (C3's instance: nothing reads it)
@@ -77,6 +83,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
   // RL: the lane's ray (o, d) as three double2, written at its refill
   __shared__ double2 ray_lds[RL ? 3 * 256 : 1];
   const uint32_t wbase = threadIdx.x & ~63u;
+  // the node block's base (the records a node step reads: DevScene::inner or innerq) and, A32, the
+  // leaf records' offset from it and the primitive records' base
+  constexpr uint32_t NODE_BYTES = Q ? sizeof(GInnerQ) : sizeof(GInner);
+  const char* const nbase = Q ? reinterpret_cast<const char*>(sc.innerq) : reinterpret_cast<const char*>(sc.inner);
+  const char* const pbase = reinterpret_cast<const char*>(sc.prims);
+  const uint32_t leaf_off0 = A32 ? (uint32_t)(reinterpret_cast<const char*>(sc.leaves) - nbase) : 0u;
   int32_t* stk = lds_stack + threadIdx.x;
   int32_t* gsp = spill + blockIdx.x * 256 + threadIdx.x;
   const uint32_t lane = threadIdx.x & 63;
@@ -113,6 +125,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
   // a 0 / 1 register and a second compare): sp < 0 marks an idle lane (busy == (sp >= 0)), and
   // a lane scans a leaf exactly while pk < pend ((busy && in_prim) == (pk < pend): a leaf holds
   // at least one primitive, and pk == pend once it is done).
+  // DIST: a step tests a leaf's primitives all at once, so the leaf being scanned is kept as its
+  // ref (lref <= -2, else 0) and decoded in the primitive step alone, not where a node step or a
+  // pop enters it (every iteration's advance): the scanning lanes are those with lref < 0.
+  int32_t lref = 0;
   int sp = -1, low = 0;
   int clean_from = 0;     // stack entries at positions >= clean_from were pushed after the last accepted hit
   int32_t bprim = -1;
@@ -141,12 +157,23 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
 #else
 #define IZPI_MARK(name) (void)0
 #endif
+  // measurement builds only (-DIZPI_TRACE_ICOUNT, tools/step_counts.py --trips): how often the wave
+  // runs each path of the loop, counted on the scalar unit and written with the frame counters
+#ifdef IZPI_TRACE_ICOUNT
+  uint32_t ic_iter = 0, ic_idle = 0, ic_dequeue = 0, ic_refill = 0, ic_twin = 0, ic_spill = 0, ic_readback = 0, ic_pop = 0, ic_finish = 0;
+#define IZPI_IC(v) (v)++
+#else
+#define IZPI_IC(v) (void)0
+#endif
   for (;;) {
     IZPI_CLK(k0);
     IZPI_MARK("head");
+    IZPI_IC(ic_iter);
     const uint64_t idle = __builtin_amdgcn_ballot_w64(sp < 0);
     uint64_t idle_now = idle;  // the idle lanes after this iteration's refill
     if (idle != 0) {
+      IZPI_MARK("idle");
+      IZPI_IC(ic_idle);
       const uint32_t nidle = (uint32_t)__popcll(idle);
       if (!exhausted && (nidle >= refill_min || idle == ~0ull) && c_pos >= c_end) {
         // the wave's private range of the queue is used up: take the next `chunk`
@@ -154,6 +181,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
         // Every wave's first chunk is its own (chunk w, set before the loop), without an
         // atomic: a pass of at most nwaves chunks (the tail passes) dequeues without any.
         IZPI_MARK("dequeue");
+        IZPI_IC(ic_dequeue);
         uint32_t b = 0;
         if (lane == 0) b = atomicAdd(wp.trace_next, chunk);
         b = __builtin_amdgcn_readfirstlane(b) + nwaves * first;
@@ -163,6 +191,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
       }
       if (!exhausted && (nidle >= refill_min || idle == ~0ull) && c_pos < c_end) {
         IZPI_MARK("refill");
+        IZPI_IC(ic_refill);
         const uint32_t take = nidle < c_end - c_pos ? nidle : c_end - c_pos;
         const uint32_t base = c_pos;
         c_pos += take;
@@ -217,7 +246,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
       }
     }
     IZPI_MARK("pick");
-    const uint64_t m_prim = __builtin_amdgcn_ballot_w64(pk < pend);
+    const uint64_t m_prim = DIST ? __builtin_amdgcn_ballot_w64(lref < 0) : __builtin_amdgcn_ballot_w64(pk < pend);
     const uint64_t m_node = ~(m_prim | idle_now);
     if ((m_prim | m_node) == 0) continue;
     const uint32_t n_prim = (uint32_t)__popcll(m_prim), n_node = (uint32_t)__popcll(m_node);
@@ -234,7 +263,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
         // ---- distributed primitive step: every pending test of the PRIM lanes' leaves
         // (up to 64) runs on its own lane, then each owner accepts its leaf's results in
         // primitive order against its running tMax (bvh4.go:123-134, triangle.go:219)
-        const uint32_t cnt = (uint32_t)(pend - pk);  // 1..4, and 0 on the lanes that scan no leaf
+        const uint32_t cnt = lref < 0 ? (uint32_t)leaf_count(lref) : 0u;  // 1..4, and 0 on the lanes that scan no leaf
+        pk = leaf_start(lref);
         // exclusive prefix sum of cnt over the wave: one ballot per bit of cnt, each counted
         // below this lane by a v_mbcnt pair
         const uint32_t base = lanes_below(__ballot(cnt & 1u)) + 2u * lanes_below(__ballot(cnt & 2u)) +
@@ -275,7 +305,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
             p0 = make_double2(a0.x, a0.y); p1 = make_double2(a1.x, a1.y); p2 = make_double2(a2.x, a2.y);
             p3 = make_double2(a3.x, a3.y); p4 = make_double2(a4.x, a4.y);
           } else {
-            const double2* pp = reinterpret_cast<const double2*>(sc.prims + pi);
+            const double2* pp = A32 ? reinterpret_cast<const double2*>(pbase + (uint32_t)pi * (uint32_t)sizeof(GPrim))
+                                    : reinterpret_cast<const double2*>(sc.prims + pi);
             p0 = pp[0]; p1 = pp[1]; p2 = pp[2]; p3 = pp[3]; p4 = pp[4];
 #ifdef IZPI_SHADOW
             if (IZPI_SHADOW & 4) {
@@ -326,7 +357,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
             bprim = pk + acc;
             clean_from = sp;
           }
-          pk = pend;
+          lref = 0;
           in_prim = false;
           advance = true;
         } else if (!TRI && served) {
@@ -353,7 +384,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
             }
             clean_from = sp;
           }
-          pk = pend;
+          lref = 0;
           in_prim = false;
           advance = true;
         }
@@ -372,7 +403,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
         const double2 r0 = rp[0], r1 = rp[1], r2 = rp[2];
         const V3 o = mk(r0.x, r0.y, r1.x), d = mk(r1.y, r2.x, r2.y);
         const double tmin = ray_tmin(wp.in, qi, lkind);
-        const double2* pp = reinterpret_cast<const double2*>(sc.prims + pk);
+        const double2* pp = A32 ? reinterpret_cast<const double2*>(pbase + (uint32_t)pk * (uint32_t)sizeof(GPrim))
+                                : reinterpret_cast<const double2*>(sc.prims + pk);
         const double2 p0 = pp[0], p1 = pp[1], p2 = pp[2], p3 = pp[3], p4 = pp[4];
         const double pa[9] = {p0.x, p0.y, p1.x, p1.y, p2.x, p2.y, p3.x, p3.y, p4.x};
         is_tri = TRI || (uint32_t)__double2loint(p4.y) == IZPI_PRIM_TRIANGLE;
@@ -402,9 +434,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
       c_nstep++;
       // ---- node step: visit `cur` (bvh4.go:87-146)
       const bool wave_fast = (m_node & m_slow) == 0;
+#ifdef IZPI_TRACE_ICOUNT
+      if (!wave_fast) ic_twin++;
+#endif
       if ((m_node & __builtin_amdgcn_ballot_w64(sp + 3 - low > S)) != 0) {
         // ring too full for this step's three writes: spill the oldest entries (rare)
+        IZPI_MARK("spill");
         any_spill = true;
+        IZPI_IC(ic_spill);
         if (busy && !in_prim) {
           while (sp + 3 - low > S) {
             gsp[(size_t)low * spill_stride] = stk[(low & (S - 1)) * 256];
@@ -415,6 +452,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
           }
         }
       }
+      IZPI_MARK("node_loads");
       if (busy && !in_prim) {
         const float tm = (float)tmax;
         // An inner node (4-slot box test) and a leaf's slot-0 re-test (A10) run as ONE
@@ -424,20 +462,30 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
         const bool is_leaf = ref_is_leaf(cur);
         float4 q0, q1, mnz_, mxx_, mxy_, mxz_;
         int4 ch_;
+        // the lane's record (lp: a leaf's GLeaf or the inner node) and the inner node's remaining
+        // loads (np: leaf lanes read them from the root node, a cached valid address; the values
+        // are not used)
+        const float4 *lp = nullptr, *np = nullptr;
+        if constexpr (!LB && A32) {
+          const uint32_t noff = is_leaf ? 0u : (uint32_t)cur * NODE_BYTES;
+          const uint32_t loff = is_leaf ? leaf_off0 + (uint32_t)leaf_start(cur) * (uint32_t)sizeof(GLeaf) : noff;
+          lp = reinterpret_cast<const float4*>(nbase + loff);
+          np = reinterpret_cast<const float4*>(nbase + noff);
+        } else if constexpr (!LB) {
+          lp = reinterpret_cast<const float4*>(is_leaf ? (const void*)(sc.leaves + leaf_start(cur))
+                                                       : Q ? (const void*)(sc.innerq + cur) : (const void*)(sc.inner + cur));
+          np = is_leaf ? reinterpret_cast<const float4*>(nbase) : lp;
+        }
         if constexpr (LB) {
-          LF4* lp = is_leaf ? l_leaves + (size_t)2 * leaf_start(cur) : l_inner + (size_t)8 * cur;
-          LF4* np = is_leaf ? l_inner : lp;
-          const v4f a0 = lp[0], a1 = lp[1], a2 = np[2], a3 = np[3], a4 = np[4], a5 = np[5], c = np[6];
+          LF4* llp = is_leaf ? l_leaves + (size_t)2 * leaf_start(cur) : l_inner + (size_t)8 * cur;
+          LF4* lnp = is_leaf ? l_inner : llp;
+          const v4f a0 = llp[0], a1 = llp[1], a2 = lnp[2], a3 = lnp[3], a4 = lnp[4], a5 = lnp[5], c = lnp[6];
           q0 = make_float4(a0.x, a0.y, a0.z, a0.w); q1 = make_float4(a1.x, a1.y, a1.z, a1.w);
           mnz_ = make_float4(a2.x, a2.y, a2.z, a2.w); mxx_ = make_float4(a3.x, a3.y, a3.z, a3.w);
           mxy_ = make_float4(a4.x, a4.y, a4.z, a4.w); mxz_ = make_float4(a5.x, a5.y, a5.z, a5.w);
           ch_ = make_int4(__float_as_int(c.x), __float_as_int(c.y), __float_as_int(c.z), __float_as_int(c.w));
         } else if constexpr (Q) {
-          // GInnerQ = (org, ex), (q mnx, mny, mnz, mxx), (q mxy, mxz, child 0, 1), (child 2, 3, -, -);
-          // leaf lanes read their last two loads from the root node (values not used)
-          const float4* lp = reinterpret_cast<const float4*>(is_leaf ? (const void*)(sc.leaves + leaf_start(cur))
-                                                                     : (const void*)(sc.innerq + cur));
-          const float4* np = is_leaf ? reinterpret_cast<const float4*>(sc.innerq) : lp;
+          // GInnerQ = (org, ex), (q mnx, mny, mnz, mxx), (q mxy, mxz, child 0, 1), (child 2, 3, -, -)
           q0 = lp[0]; q1 = lp[1];
           const float4 c2 = np[2], c3 = np[3];
           const uint32_t ex = __float_as_uint(q0.w);
@@ -459,11 +507,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
           mnz_ = dmnz; mxx_ = dmxx; mxy_ = dmxy; mxz_ = dmxz;
           ch_ = make_int4(__float_as_int(c2.z), __float_as_int(c2.w), __float_as_int(c3.x), __float_as_int(c3.y));
         } else {
-          const float4* lp = reinterpret_cast<const float4*>(is_leaf ? (const void*)(sc.leaves + leaf_start(cur))
-                                                                     : (const void*)(sc.inner + cur));
-          // leaf lanes read their last five loads from the root node (a cached valid address;
-          // the values are not used)
-          const float4* np = is_leaf ? reinterpret_cast<const float4*>(sc.inner) : lp;
           q0 = lp[0]; q1 = lp[1];
           mnz_ = np[2]; mxx_ = np[3]; mxy_ = np[4]; mxz_ = np[5];
           ch_ = *reinterpret_cast<const int4*>(np + 6);
@@ -493,8 +536,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
         // build each bit and a compare to test it again at every use.
         uint64_t hit[4];
         if (wave_fast) {
+          IZPI_MARK("slab_fast");
           slab4_fast(mnx, mny, mnz, mxx, mxy, mxz, ox, oy, oz, ix, iy, iz, tm, hit);
         } else {
+          IZPI_MARK("slab_twin");
           const float amnx[4] = {mnx.x, mnx.y, mnx.z, mnx.w}, amny[4] = {mny.x, mny.y, mny.z, mny.w},
                       amnz[4] = {mnz.x, mnz.y, mnz.z, mnz.w}, amxx[4] = {mxx.x, mxx.y, mxx.z, mxx.w},
                       amxy[4] = {mxy.x, mxy.y, mxy.z, mxy.w}, amxz[4] = {mxz.x, mxz.y, mxz.z, mxz.w};
@@ -502,6 +547,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
           for (int i = 0; i < 4; i++)
             hit[i] = __builtin_amdgcn_ballot_w64(slab(amnx[i], amny[i], amnz[i], amxx[i], amxy[i], amxz[i], ox, oy, oz, ix, iy, iz, tm));
         }
+        IZPI_MARK("node_tail");
         // slots 0..3 with ChildIndex != -1 whose box is hit (bvh4.go:119-146): the first
         // is visited next, the others are pushed in slot order (popped LIFO). Selects
         // instead of branches: each divergent branch costs exec-mask and lane-mask
@@ -522,8 +568,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
         const bool enter = ref_is_leaf(next) && (is_leaf || sc.leaf_shortcut);
         leaf_next = enter && !is_leaf;
         in_prim = enter;
-        pk = enter ? leaf_start(next) : pk;
-        pend = enter ? leaf_start(next) + leaf_count(next) : pend;
+        if constexpr (DIST) {
+          lref = enter ? next : lref;
+        } else {
+          pk = enter ? leaf_start(next) : pk;
+          pend = enter ? leaf_start(next) + leaf_count(next) : pend;
+        }
         next = enter ? -1 : next;
         // the other hit children, compacted in slot order, are written unconditionally to
         // ring positions sp..sp+2 (the ring keeps 3 free entries above sp); sp moves by
@@ -555,7 +605,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
       // drains every store)
       const int spn = sp - 1;
       int32_t top = *(volatile __attribute__((address_space(3))) int32_t*)&lds_stack[threadIdx.x + (spn & (S - 1)) * 256];
+#ifdef IZPI_TRACE_ICOUNT
+      if (__ballot(do_pop) != 0) ic_pop++;
+      if (__ballot(do_fin) != 0) ic_finish++;
+#endif
       if (any_spill && __ballot(do_pop && spn < low) != 0) {
+        IZPI_MARK("readback");
+        IZPI_IC(ic_readback);
         if (do_pop && spn < low) {
           top = gsp[(size_t)spn * spill_stride];
           low = spn;
@@ -565,6 +621,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
         }
         __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) here, not for every pop
       }
+      IZPI_MARK("advance_tail");
       cur = (advance && next != -1) ? next : (do_pop ? top : cur);
       sp = (advance && next == -1) ? spn : sp;  // a pop, or the ray is done: sp == -1, the lane is idle
       // An entry pushed after the last accepted hit meets the same tMax it was pushed
@@ -572,10 +629,15 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
       const bool lf = do_pop && ref_is_leaf(top) && spn >= clean_from && sc.leaf_shortcut;
       in_prim = in_prim || lf;
       leaf_next = leaf_next || lf;
-      pk = lf ? leaf_start(top) : pk;
-      pend = lf ? leaf_start(top) + leaf_count(top) : pend;
+      if constexpr (DIST) {
+        lref = lf ? top : lref;
+      } else {
+        pk = lf ? leaf_start(top) : pk;
+        pend = lf ? leaf_start(top) + leaf_count(top) : pend;
+      }
       clean_from = (do_pop && spn < clean_from) ? spn : clean_from;
       if (do_fin) {
+        IZPI_MARK("finish");
         const double2 uv = (UVL && bprim >= 0) ? lds_uv[threadIdx.x] : make_double2(0.0, 0.0);
         if ((UVL || UVS) && wp.hit_uv) {  // (t, prim) and (u, v) in one 32-B record (hs == 2)
           double2* rec = wp.in.hit + ((size_t)qi << 1);
@@ -587,7 +649,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
         busy = false;
       }
     }
-    const uint64_t n_short = (uint64_t)__popcll(__ballot(leaf_next));  // leaf visits taken by a shortcut
+    IZPI_MARK("advance_end");
+    const uint64_t n_short = (uint64_t)__popcll(__builtin_amdgcn_ballot_w64(leaf_next));  // leaf visits taken by a shortcut
     c_nodes += n_short;
     c_short += n_short;
 #ifdef IZPI_TRACE_CLOCKS
@@ -607,6 +670,20 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
     if (c_spill_st) atomicAdd(counters + CNT_CLK_REFILL, (unsigned long long)c_spill_st);
     if (c_spill_ld) atomicAdd(counters + CNT_CLK_NODE, (unsigned long long)c_spill_ld);
     if (sh_acc == 0x9E3779B9u) atomicOr(err, 0u);
+  }
+#endif
+#ifdef IZPI_TRACE_ICOUNT
+  if (lane == 0) {  // (node steps on the fast slab: CNT_NSTEP less the twin's; primitive steps: CNT_PSTEP)
+    count_add(wp.cpart, counters, CNT_IC_ITER, ic_iter);
+    count_add(wp.cpart, counters, CNT_IC_IDLE, ic_idle);
+    count_add(wp.cpart, counters, CNT_IC_DEQUEUE, ic_dequeue);
+    count_add(wp.cpart, counters, CNT_IC_REFILL, ic_refill);
+    count_add(wp.cpart, counters, CNT_IC_TWIN, ic_twin);
+    count_add(wp.cpart, counters, CNT_IC_SPILL, ic_spill);
+    count_add(wp.cpart, counters, CNT_IC_READBACK, ic_readback);
+    count_add(wp.cpart, counters, CNT_IC_POP, ic_pop);
+    count_add(wp.cpart, counters, CNT_IC_FINISH, ic_finish);
+    count_add(wp.cpart, counters, CNT_IC_WAVES, 1);
   }
 #endif
   if (lane == 0) {
@@ -630,6 +707,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
 // The BVH-in-LDS ray instances run an 8-entry stack ring: their trees (at most 4 KB) are
 // too shallow to fill it, and the 8 KB it frees hold the rays (still 5 blocks per CU).
 constexpr int ring_of(bool lb, bool rl) { return lb && rl ? 8 : TRACE_RING; }
+int trace_ring(const Tracer& t) { return ring_of(t.lds_bvh, t.ray_lds); }
 
 // Pick the k_trace2 instance and its grid (no allocation: the caller grows d_spill to
 // t->spill_bytes).
@@ -654,6 +732,9 @@ int make_tracer(izpi_ctx* ctx, const izpi_render_tuning& tu, bool need_uv, Trace
   // a quantised scene's 64-B nodes (the 128-B records hold the same decoded boxes: the
   // other instances traverse the same tree)
   t->qnodes = ctx->sc.quantized && t->p2 && !t->lds_bvh && !(tu.flags & IZPI_TUNE_NO_QNODES);
+  // 32-bit record offsets where the uploaded scene allows them (IZPI_TUNE_WIDE_ADDR: the 64-bit
+  // addresses of a scene past 4 GiB, for tests)
+  t->a32 = ctx->sc.addr32 != 0 && !(tu.flags & IZPI_TUNE_WIDE_ADDR);
   if (tu.prim_weight) t->prim_w = tu.prim_weight;
   if (tu.trace_chunk) t->tchunk = tu.trace_chunk;
   if (tu.refill_min) t->refill_min = std::min<uint32_t>(64, tu.refill_min);
@@ -661,7 +742,8 @@ int make_tracer(izpi_ctx* ctx, const izpi_render_tuning& tu, bool need_uv, Trace
   ctx->err = "no k_trace2 instance for this scene and tuning";
 #define IZPI_T2_OCC(P, T, L, R, Q)                                                               \
   if (t->p2 == P && t->tri == T && t->lds_bvh == L && t->ray_lds == R && t->qnodes == Q) \
-    rc = resident_blocks(ctx, k_trace2<ring_of(L, R), TRACE_WPE, P, T, L, R, Q>, &t->blocks);
+    rc = t->a32 ? resident_blocks(ctx, k_trace2<ring_of(L, R), TRACE_WPE, P, T, L, R, Q, !L>, &t->blocks)       \
+                : resident_blocks(ctx, k_trace2<ring_of(L, R), TRACE_WPE, P, T, L, R, Q, false>, &t->blocks);
   IZPI_T2_LIST(IZPI_T2_OCC)
 #undef IZPI_T2_OCC
   if (rc) return rc;
@@ -674,8 +756,12 @@ void launch_trace(izpi_ctx* ctx, const DevScene& sc, const Tracer& t, const Wave
   const uint32_t stride = (uint32_t)t.blocks * 256;
 #define IZPI_T2_LAUNCH(P, T, L, R, Q)                                                                          \
   if (t.p2 == P && t.tri == T && t.lds_bvh == L && t.ray_lds == R && t.qnodes == Q) {                          \
-    hipLaunchKernelGGL((k_trace2<ring_of(L, R), TRACE_WPE, P, T, L, R, Q>), g, b, 0, st, sc, wp, ctx->d_counters, \
-                       misc(ctx, 1), spill, stride, t.prim_w, t.tchunk, t.refill_min);                        \
+    if (t.a32)                                                                                                 \
+      hipLaunchKernelGGL((k_trace2<ring_of(L, R), TRACE_WPE, P, T, L, R, Q, !L>), g, b, 0, st, sc, wp,           \
+                         ctx->d_counters, misc(ctx, 1), spill, stride, t.prim_w, t.tchunk, t.refill_min);       \
+    else                                                                                                       \
+      hipLaunchKernelGGL((k_trace2<ring_of(L, R), TRACE_WPE, P, T, L, R, Q, false>), g, b, 0, st, sc, wp,        \
+                         ctx->d_counters, misc(ctx, 1), spill, stride, t.prim_w, t.tchunk, t.refill_min);       \
     return;                                                                                                    \
   }
   IZPI_T2_LIST(IZPI_T2_LAUNCH)
