@@ -147,8 +147,10 @@ enum {
                                      instead of the 64-B quantised ones (the same boxes) */
   IZPI_TUNE_NO_SHADE_STAGE = 2048,/* forward Colour renders: k_shade reserves its output entries every block-iteration
                                      instead of every other one with the first's entries staged in LDS */
-  IZPI_TUNE_WIDE_ADDR = 4096      /* k_trace2 forms the 64-bit record addresses of a scene whose arrays pass 4 GiB,
+  IZPI_TUNE_WIDE_ADDR = 4096,     /* k_trace2 forms the 64-bit record addresses of a scene whose arrays pass 4 GiB,
                                      not 32-bit offsets from a scalar base */
+  IZPI_TUNE_LEAF4 = 8192          /* k_trace2's distributed primitive step sized for leaves of four primitives on a
+                                     scene whose leaves hold at most three */
 };
 
 typedef struct izpi_render_req {

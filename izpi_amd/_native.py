@@ -106,6 +106,7 @@ TUNE_NO_PRIM_LDS = 256
 TUNE_NO_QNODES = 1024
 TUNE_NO_SHADE_STAGE = 2048
 TUNE_WIDE_ADDR = 4096
+TUNE_LEAF4 = 8192
 
 
 def tuning(**kw):

@@ -44,6 +44,8 @@ struct DevScene {
   uint32_t quantized;           // IZPI_SCENE_QUANTIZED_BVH: `inner` holds the decoded boxes of `innerq`
   uint32_t addr32;              // inner, innerq and leaves are one block under 4 GiB, as are prims (trace_addr32):
                                 // k_trace2 addresses their records by 32-bit byte offsets (fills the struct's tail padding)
+  uint32_t leaf_max;            // the largest primitive count of a leaf, 0 for an empty scene (make_tracer: at most 3, as
+                                // the GPU builder's trees have, picks the primitive step sized for three)
 #ifdef IZPI_SHADOW
   // measurement builds only (byte breakdown): copies of the traversal arrays that
   // k_trace2 reads beside the real ones, so a class's bytes past L2 show as extra FETCH_SIZE

@@ -671,8 +671,8 @@ int render_body(izpi_ctx* ctx, const izpi_render_req* req, const RenderCall& cal
   const double t_tiles = host_ms();
   if ((rc = make_tracer(ctx, tu, !ctx->sc.tri_only || ctx->any_uv, &tr))) return rc;
   if (pass_log)  // diagnostics: the k_trace2 instance this render runs
-    fprintf(stderr, "IZPI_TRACE_INSTANCE dist=%d tri=%d lds_bvh=%d ray_lds=%d q=%d\nIZPI_TRACE_ADDR a32=%d ring=%d\n", (int)tr.p2, (int)tr.tri,
-            (int)tr.lds_bvh, (int)tr.ray_lds, (int)tr.qnodes, (int)(tr.a32 && !tr.lds_bvh), trace_ring(tr));
+    fprintf(stderr, "IZPI_TRACE_INSTANCE dist=%d tri=%d lds_bvh=%d ray_lds=%d q=%d\nIZPI_TRACE_ADDR a32=%d ring=%d\nIZPI_TRACE_LEAVES leaf_max=%u leaf3=%d tmin_fixed=%d\n", (int)tr.p2, (int)tr.tri,
+            (int)tr.lds_bvh, (int)tr.ray_lds, (int)tr.qnodes, (int)(tr.a32 && !tr.lds_bvh), trace_ring(tr), ctx->sc.leaf_max, (int)tr.leaf3, (int)(ctx->sc.no_pathlen != 0));
   const double t_tracer = host_ms();
   // Plan: the family's cached plan when the request has its shape, else from the free memory.
   PlanCache& cache = ctx->plans[rs.preview];
@@ -767,10 +767,10 @@ int render_body(izpi_ctx* ctx, const izpi_render_req* req, const RenderCall& cal
   fprintf(stderr, "IZPI_SHADOW spill_stores %llu spill_loads %llu (entries)\n", cnt[CNT_CLK_REFILL], cnt[CNT_CLK_NODE]);
 #endif
 #ifdef IZPI_TRACE_ICOUNT
-  fprintf(stderr, "IZPI_TRACE_ICOUNT {\"iterations\": %llu, \"idle\": %llu, \"dequeue\": %llu, \"refill\": %llu, \"prim\": %llu, \"node_fast\": %llu, "
-          "\"node_twin\": %llu, \"spill\": %llu, \"readback\": %llu, \"pop\": %llu, \"finish\": %llu, \"waves\": %llu}\n",
-          cnt[CNT_IC_ITER], cnt[CNT_IC_IDLE], cnt[CNT_IC_DEQUEUE], cnt[CNT_IC_REFILL], cnt[CNT_PSTEP], cnt[CNT_NSTEP] - cnt[CNT_IC_TWIN], cnt[CNT_IC_TWIN],
-          cnt[CNT_IC_SPILL], cnt[CNT_IC_READBACK], cnt[CNT_IC_POP], cnt[CNT_IC_FINISH], cnt[CNT_IC_WAVES]);
+  fprintf(stderr, "IZPI_TRACE_ICOUNT {\"iterations\": %llu, \"due\": %llu, \"dequeue\": %llu, \"refill\": %llu, \"prim\": %llu, \"node_fast\": %llu, "
+          "\"node_twin\": %llu, \"spill\": %llu, \"readback\": %llu, \"spilled\": %llu, \"pop\": %llu, \"finish\": %llu, \"waves\": %llu}\n",
+          cnt[CNT_IC_ITER], cnt[CNT_IC_DUE], cnt[CNT_IC_DEQUEUE], cnt[CNT_IC_REFILL], cnt[CNT_PSTEP], cnt[CNT_NSTEP] - cnt[CNT_IC_TWIN], cnt[CNT_IC_TWIN],
+          cnt[CNT_IC_SPILL], cnt[CNT_IC_READBACK], cnt[CNT_IC_SPILLED], cnt[CNT_IC_POP], cnt[CNT_IC_FINISH], cnt[CNT_IC_WAVES]);
 #endif
 #ifdef IZPI_TRACE_CLOCKS
   fprintf(stderr, "IZPI_TRACE_CLOCKS refill %llu node %llu prim %llu advance %llu (wave cycles)\n", cnt[CNT_CLK_REFILL],
@@ -1209,7 +1209,7 @@ int upload_packed(izpi_ctx* ctx, const izpi_scene_desc* d, const PackedScene& ps
   sc.spd_wl = dswl; sc.spd_val = dsv;
   sc.root = ps.root; sc.num_inner = ps.num_inner; sc.num_prims = d->num_prims; sc.num_lights = d->num_lights;
   sc.quantized = ps.quantized; sc.leaf_shortcut = ps.leaf_shortcut; sc.nan_free_bounds = ps.nan_free_bounds;
-  sc.tri_only = ps.tri_only; sc.time_free = ps.time_free; sc.no_pathlen = ps.no_pathlen;
+  sc.tri_only = ps.tri_only; sc.time_free = ps.time_free; sc.no_pathlen = ps.no_pathlen; sc.leaf_max = ps.leaf_max;
   sc.addr32 = trace_addr32(ps.inner.size(), ps.innerq.size(), ps.leaves.size(), ps.prims.size());
   sc.cam = d->camera;
   ctx->d_triverts = dtv;

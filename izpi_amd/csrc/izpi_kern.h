@@ -103,7 +103,7 @@ enum { CNT_RAYS = 0, CNT_NODES, CNT_TRI, CNT_SPH, CNT_LTRI, CNT_LSPH, CNT_NSTEP,
 // CNT_NSTEP: those must stay what they are, one count per wave and step, added by lane 0.
 enum { CNT_IC_ITER = CNT_CLK_REFILL, CNT_IC_DEQUEUE = CNT_CLK_NODE, CNT_IC_REFILL = CNT_CLK_PRIM, CNT_IC_TWIN = CNT_CLK_ADV,
        CNT_IC_SPILL = CNT_SCLK_ITEM, CNT_IC_READBACK = CNT_SCLK_REFILL, CNT_IC_POP = CNT_SCLK_PUSH, CNT_IC_FINISH = CNT_SCLK_MAT,
-       CNT_IC_WAVES = CNT_SCLK_FIN, CNT_IC_IDLE = CNT_SCLK_MIX };
+       CNT_IC_WAVES = CNT_SCLK_FIN, CNT_IC_DUE = CNT_SCLK_MIX, CNT_IC_SPILLED = CNT_SCLK_LPDF };
 #if defined(IZPI_TRACE_CLOCKS) || defined(IZPI_SHADE_CLOCKS) || defined(IZPI_SHADOW)
 #error "IZPI_TRACE_ICOUNT shares counter rows with the clock and shadow builds"
 #endif
@@ -1654,6 +1654,7 @@ struct Tracer {
   bool ray_lds = false;  // RL
   bool qnodes = false;   // Q
   bool a32 = false;      // A32 (the BVH-in-LDS instances read no record from global memory: compiled without)
+  bool leaf3 = false;    // L3 (the distributed-leaf instances)
   // queue entries per dequeue and idle lanes per refill, measured on C3: chunk 128 / refill
   // 16 -> 211 ms of k_trace2 per frame, 512 / 24 -> 201, 1024 -> 207, 2048 -> 216, 64 -> 303
   uint32_t prim_w = 32, tchunk = 512, refill_min = 24;

@@ -50,6 +50,7 @@ int split_bvh(const izpi_scene_desc* d, PackedScene* out, std::vector<int32_t>& 
       if (st < 0 || (uint64_t)st + (uint64_t)cnt > d->num_prims) return fail(err, IZPI_ERR_INVALID, "leaf primitive range out of bounds");
       if (cnt > 7 || st >= (1 << 27)) return fail(err, IZPI_ERR_UNSUPPORTED, "leaf too large for the leaf-ref encoding");
       ref[k] = make_leaf_ref(st, cnt);
+      out->leaf_max = std::max(out->leaf_max, (uint32_t)cnt);
     } else {
       for (int i = 0; i < 4; i++)
         if (n.prim_count[i] != 0) return fail(err, IZPI_ERR_INVALID, "inner node with a primitive slot");

@@ -34,6 +34,7 @@ struct PackedScene {
   int32_t root = -1;
   uint32_t num_inner = 0, leaf_shortcut = 1, quantized = 0, nan_free_bounds = 1, time_free = 1, no_pathlen = 1, tri_only = 1;
   uint32_t stack_needed = 0;             // stack_bound of the tree
+  uint32_t leaf_max = 0;                 // the largest primitive count of a leaf (0: no leaf)
   // what the materials allow and need: the kernel instances a render picks
   bool mat_ok_rgb = true, mat_ok_spectral = true;  // every material has the textures the Colour / Spectral sampler reads
   bool basic_materials = true;           // only Lambertian + DiffuseLight

@@ -32,6 +32,13 @@
 // scalar base plus one unsigned 32-bit byte offset per lane (the `saddr` form of global_load)
 // instead of a sign extension, a 64-bit shift and a 64-bit add per lane, formed once for leaf
 // and inner lanes alike inside exec-masked regions. Larger scenes keep the 64-bit addresses.
+// L3: no leaf of the scene holds more than three primitives (DevScene::leaf_max, the GPU builder's
+// trees), so the distributed primitive step sums two bits of the leaf sizes instead of three and
+// writes, reads back and accepts three entries per leaf instead of four.
+// FT: every ray's tMin is the sampler rays' 0.001, since the scene has no dielectric (no path-length
+// ray, DevScene::no_pathlen) and the launch no per-entry bounds (WaveBuf::tminmax), so a primitive
+// test fetches neither its owner's kind word nor, with the ray in LDS, its entry. Compiled with L3
+// only: the trees that are traced for speed are the GPU builder's.
 constexpr uint32_t BVH_LDS_BYTES = 4096;
 // This lane's bit of a wave mask, as a condition (the mask becomes the select's lane mask).
 __device__ __forceinline__ bool lane_of(uint64_t mask) { return __builtin_amdgcn_inverse_ballot_w64(mask); }
@@ -40,7 +47,7 @@ __device__ __forceinline__ bool lane_of(uint64_t mask) { return __builtin_amdgcn
 __device__ __forceinline__ uint32_t lanes_below(uint64_t mask) {
   return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
 }
-template <int S, int WPE, bool DIST, bool TRI, bool LB, bool RL, bool Q, bool A32>
+template <int S, int WPE, bool DIST, bool TRI, bool LB, bool RL, bool Q, bool A32, bool L3, bool FT>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) k_trace2(const DevScene sc, const WaveParams wp, unsigned long long* counters,
                                                 uint32_t* err, int32_t* spill, uint32_t spill_stride, uint32_t prim_w,
                                                 uint32_t tchunk, uint32_t refill_min) {
@@ -49,6 +56,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
   static_assert(!RL || (DIST && (TRI || LB)), "the LDS-resident ray instances: triangle-only global BVH, or the BVH in LDS");
   static_assert(!Q || !LB, "the quantised nodes are read from global memory");
   static_assert(!A32 || !LB, "the 32-bit offsets address records in global memory");
+  static_assert(!L3 || DIST, "the leaf size bound shapes the distributed primitive step");
+  static_assert(!FT || L3, "the fixed tMin is compiled for the three-primitive leaf instances");
+  constexpr uint32_t LEAF_MAX = L3 ? 3 : 4;  // entries a leaf can put into a batch
   // (u, v) of the accepted hit: kept in lds_uv until the ray finishes (UVL), stored to the
   // hit record at acceptance (UVS: the BVH-in-LDS ray instance, whose steps issue no global
   // loads for the store to hold up), or not kept (C3's instance: nothing reads it)
@@ -113,7 +123,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
   if ((uint64_t)(blockIdx.x * 4u + (threadIdx.x >> 6)) * first >= n) return;
   uint64_t c_rays = 0, c_nodes = 0, c_tri = 0, c_sph = 0;  // wave-uniform (SGPR)
   uint64_t c_nstep = 0, c_pstep = 0, c_short = 0;
-  bool busy = false, in_prim = false;
+  // The lanes that scanned a leaf after the last step, before its advance (wave-uniform): a lane
+  // that scans one at the next pick and is not among them was sent there by a pop's shortcut.
+  uint64_t m_scan = 0;
   bool exhausted = false;
   uint32_t qi = 0;        // the lane's queue entry (its ray, hit and path state index)
   uint32_t lkind = RAY_MAIN;
@@ -122,9 +134,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
   int32_t cur = -1, pk = 0, pend = 0;
   // The wave's mode masks are ballots of single compares on these registers (a compare leaves
   // its lane mask as it is; the ballot of a boolean that went through a join is rebuilt through
-  // a 0 / 1 register and a second compare): sp < 0 marks an idle lane (busy == (sp >= 0)), and
-  // a lane scans a leaf exactly while pk < pend ((busy && in_prim) == (pk < pend): a leaf holds
-  // at least one primitive, and pk == pend once it is done).
+  // a 0 / 1 register and a second compare): sp < 0 marks an idle lane, and a lane scans a leaf
+  // exactly while pk < pend (a leaf holds at least one primitive, and pk == pend once it is
+  // done). The steps and the refill take their lanes from these masks (lane_of): no per-lane
+  // `busy` or `in primitive mode` flag is carried round the loop.
   // DIST: a step tests a leaf's primitives all at once, so the leaf being scanned is kept as its
   // ref (lref <= -2, else 0) and decoded in the primitive step alone, not where a node step or a
   // pop enters it (every iteration's advance): the scanning lanes are those with lref < 0.
@@ -160,7 +173,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
   // measurement builds only (-DIZPI_TRACE_ICOUNT, tools/step_counts.py --trips): how often the wave
   // runs each path of the loop, counted on the scalar unit and written with the frame counters
 #ifdef IZPI_TRACE_ICOUNT
-  uint32_t ic_iter = 0, ic_idle = 0, ic_dequeue = 0, ic_refill = 0, ic_twin = 0, ic_spill = 0, ic_readback = 0, ic_pop = 0, ic_finish = 0;
+  uint32_t ic_iter = 0, ic_due = 0, ic_spilled = 0, ic_dequeue = 0, ic_refill = 0, ic_twin = 0, ic_spill = 0, ic_readback = 0, ic_pop = 0, ic_finish = 0;
 #define IZPI_IC(v) (v)++
 #else
 #define IZPI_IC(v) (void)0
@@ -171,11 +184,18 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
     IZPI_IC(ic_iter);
     const uint64_t idle = __builtin_amdgcn_ballot_w64(sp < 0);
     uint64_t idle_now = idle;  // the idle lanes after this iteration's refill
-    if (idle != 0) {
-      IZPI_MARK("idle");
-      IZPI_IC(ic_idle);
-      const uint32_t nidle = (uint32_t)__popcll(idle);
-      if (!exhausted && (nidle >= refill_min || idle == ~0ull) && c_pos >= c_end) {
+    // The exit is tested here, at the loop's head, not behind the refill: with the break inside
+    // the nested tests the compiler keeps the lane state in two sets of registers and copies
+    // between them in every iteration.
+    if (exhausted && idle == ~0ull) break;
+    // One wave-uniform test per iteration: a refill or a dequeue is due once refill_min lanes are
+    // idle (1 <= refill_min <= 64: make_tracer, so a wave with every lane idle passes it and a
+    // wave with none does not).
+    const uint32_t nidle = (uint32_t)__popcll(idle);
+    if (nidle >= refill_min && !exhausted) {
+      IZPI_MARK("due");
+      IZPI_IC(ic_due);
+      if (c_pos >= c_end) {
         // the wave's private range of the queue is used up: take the next `chunk`
         // entries with one atomic (a single head word saturates near 88 dequeues/us).
         // Every wave's first chunk is its own (chunk w, set before the loop), without an
@@ -189,7 +209,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
         c_pos = b;
         c_end = b + chunk < n ? b + chunk : n;
       }
-      if (!exhausted && (nidle >= refill_min || idle == ~0ull) && c_pos < c_end) {
+      if (!exhausted) {  // (c_pos < c_end: the range in hand, or the one just taken)
         IZPI_MARK("refill");
         IZPI_IC(ic_refill);
         const uint32_t take = nidle < c_end - c_pos ? nidle : c_end - c_pos;
@@ -198,7 +218,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
         bool main_ray = false;
         const uint32_t rank = lanes_below(idle);
         const uint32_t my = base + rank;
-        if (!busy && rank < take) {
+        if (lane_of(idle) && rank < take) {
           const uint32_t k = read_kind ? sld(wp.in.kind + my) : (uint32_t)RAY_MAIN;
           // a parked entry is not traced: its hit record (copied by k_shade) stays for the retry
           // (RL: the ray is read once, here, so it is a streamed load; otherwise primitive
@@ -221,11 +241,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
             ox = (float)r.o[0]; oy = (float)r.o[1]; oz = (float)r.o[2];
             fast = sc.nan_free_bounds && ray_fast_ok(ox, oy, oz, ix, iy, iz);
             cur = sc.root;
-            busy = cur != -1;
-            sp = busy ? 0 : -1; low = 0; clean_from = 0;
-            in_prim = false;
+            sp = cur != -1 ? 0 : -1; low = 0; clean_from = 0;
             bprim = -1;
-            if (!busy) {
+            if (cur == -1) {  // an empty scene: the ray is done at once
               if ((UVL || UVS) && wp.hit_uv) {  // (t, prim) and (u, v) interleaved: hs == 2
                 double2* rec = wp.in.hit + ((size_t)my << 1);
                 sst(rec, hit_pack(0.0, -1)); sst(rec + 1, make_double2(0.0, 0.0));
@@ -241,17 +259,24 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
         // drain the new rays' loads here: left pending they make the compiler wait for
         // vmcnt(0) at the loop head, i.e. for every hit-record store, on every iteration
         __builtin_amdgcn_s_waitcnt(0x0F70);
-      } else if (exhausted && idle == ~0ull) {
-        break;
       }
     }
     IZPI_MARK("pick");
     const uint64_t m_prim = DIST ? __builtin_amdgcn_ballot_w64(lref < 0) : __builtin_amdgcn_ballot_w64(pk < pend);
     const uint64_t m_node = ~(m_prim | idle_now);
+    {  // leaf visits the last iteration's pops took by a shortcut: counted here from the mode mask
+       // this pick needs anyway, not by a ballot of their own behind the advance
+      const uint64_t n_short = (uint64_t)__popcll(m_prim & ~m_scan);
+      c_nodes += n_short;
+      c_short += n_short;
+      m_scan = m_prim;
+    }
     if ((m_prim | m_node) == 0) continue;
     const uint32_t n_prim = (uint32_t)__popcll(m_prim), n_node = (uint32_t)__popcll(m_node);
-    bool advance = false;   // lane finished its current node / leaf: take next or pop
-    bool leaf_next = false; // the step went straight into a leaf whose re-test is known to pass
+    // The step's outcome as wave masks (wave-uniform, set in the branch the wave takes): the lanes
+    // that go down to a hit child (next != -1), and those that finished their node or leaf with
+    // no child to visit: they pop, or their ray is done.
+    uint64_t m_down = 0, m_up = 0;
     int32_t next = -1;
 #ifdef IZPI_TRACE_CLOCKS
     IZPI_CLK(k1); k_refill += k1 - k0; k0 = k1;
@@ -263,30 +288,34 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
         // ---- distributed primitive step: every pending test of the PRIM lanes' leaves
         // (up to 64) runs on its own lane, then each owner accepts its leaf's results in
         // primitive order against its running tMax (bvh4.go:123-134, triangle.go:219)
-        const uint32_t cnt = lref < 0 ? (uint32_t)leaf_count(lref) : 0u;  // 1..4, and 0 on the lanes that scan no leaf
+        const uint32_t cnt = lref < 0 ? (uint32_t)leaf_count(lref) : 0u;  // 1..LEAF_MAX, and 0 on the lanes that scan no leaf
         pk = leaf_start(lref);
         // exclusive prefix sum of cnt over the wave: one ballot per bit of cnt, each counted
-        // below this lane by a v_mbcnt pair
-        const uint32_t base = lanes_below(__ballot(cnt & 1u)) + 2u * lanes_below(__ballot(cnt & 2u)) +
-                              4u * lanes_below(__ballot(cnt & 4u));
+        // below this lane by a v_mbcnt pair (L3: cnt has two bits)
+        uint32_t base = lanes_below(__ballot(cnt & 1u)) + 2u * lanes_below(__ballot(cnt & 2u));
+        if constexpr (!L3) base += 4u * lanes_below(__ballot(cnt & 4u));
         // (the first scanning lane is always served: the mask is not empty)
         const uint64_t ms = m_prim & __builtin_amdgcn_ballot_w64(base + cnt <= 64);
         const bool served = lane_of(ms);
         const int last = 63 - __clzll((long long)ms);
         const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)(base + cnt), last);  // (wave-uniform)
-        {  // a leaf has 1..4 primitives (bvh4.go:638): four predicated writes, no loop
+        {  // a leaf has 1..4 primitives (bvh4.go:638): LEAF_MAX predicated writes, no loop
           const uint32_t e = ((uint32_t)pk << 6) | lane;
           uint32_t* dq = dist_owner + wbase + base;
           if (served) dq[0] = e;
           if (served && cnt > 1) dq[1] = e + 64u;
           if (served && cnt > 2) dq[2] = e + 128u;
-          if (served && cnt > 3) dq[3] = e + 192u;
+          if constexpr (!L3)
+            if (served && cnt > 3) dq[3] = e + 192u;
         }
         __builtin_amdgcn_wave_barrier();
         const uint32_t ent = lane < total ? dist_owner[wbase + lane] : lane;
         const uint32_t ow = ent & 63u;
-        const uint32_t oqi = (uint32_t)__shfl((int)qi, (int)ow);
-        const uint32_t okind = (uint32_t)__shfl((int)lkind, (int)ow);
+        // the owner's entry and kind word: for its tMin unless that is fixed, and the entry for
+        // the ray (unless it is in LDS) and the ray time as well
+        uint32_t oqi = 0, okind = (uint32_t)RAY_MAIN;
+        if constexpr (!RL || !FT) oqi = (uint32_t)__shfl((int)qi, (int)ow);
+        if constexpr (!FT) okind = (uint32_t)__shfl((int)lkind, (int)ow);
         if (lane < total) {
           const int32_t pi = (int32_t)(ent >> 6);
           double2 r0, r1, r2;
@@ -297,7 +326,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
             const double2* rp = reinterpret_cast<const double2*>(wp.in.ray + oqi);
             r0 = rp[0]; r1 = rp[1]; r2 = rp[2];
           }
-          const double otmin = ray_tmin(wp.in, oqi, okind);
+          const double otmin = FT ? 0.001 : ray_tmin(wp.in, oqi, okind);
           double2 p0, p1, p2, p3, p4;
           if constexpr (LB) {
             LD2* pp = l_prims + (size_t)5 * pi;
@@ -342,13 +371,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
           // triangles only: the leaf's flags and distances come in one LDS round trip, the
           // ordered accept runs in registers, and only the accepted (u, v) is read back
           const uint32_t j0 = wbase + base;
-          uint32_t f[4];
-          double tt[4];
+          uint32_t f[LEAF_MAX];
+          double tt[LEAF_MAX];
 #pragma unroll
-          for (uint32_t i = 0; i < 4; i++) { f[i] = dist_owner[j0 + i]; tt[i] = dist_t[j0 + i]; }
+          for (uint32_t i = 0; i < LEAF_MAX; i++) { f[i] = dist_owner[j0 + i]; tt[i] = dist_t[j0 + i]; }
           int32_t acc = -1;
 #pragma unroll
-          for (uint32_t i = 0; i < 4; i++)  // reject only `t > tMax` (triangle.go:219), in primitive order
+          for (uint32_t i = 0; i < LEAF_MAX; i++)  // reject only `t > tMax` (triangle.go:219), in primitive order
             if (i < cnt && (f[i] & 1u) && !(tt[i] > tmax)) { tmax = tt[i]; acc = (int32_t)i; }
           if (acc >= 0) {
             if constexpr (UVL) lds_uv[threadIdx.x] = make_double2(dist_u[j0 + acc], dist_v[j0 + acc]);
@@ -358,8 +387,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
             clean_from = sp;
           }
           lref = 0;
-          in_prim = false;
-          advance = true;
         } else if (!TRI && served) {
           int32_t acc = -1;
           double acc_u = 0, acc_v = 0;
@@ -385,17 +412,17 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
             clean_from = sp;
           }
           lref = 0;
-          in_prim = false;
-          advance = true;
         }
         __builtin_amdgcn_wave_barrier();
+        m_scan = m_prim & ~ms;  // the served lanes are done with their leaves
+        m_up = ms;
         c_tri += total - n_sph_tests;
         c_sph += n_sph_tests;
         c_pstep++;
       } else {
       // ---- primitive step: one Hit() per PRIM lane (bvh4.go:123-134)
       bool is_tri = false;
-      if (busy && in_prim) {
+      if (lane_of(m_prim)) {
         // the f64 ray is re-read here (L2) instead of living in 14 VGPRs across node steps
         // (measured: keeping it in LDS instead makes k_shade's later read of the same
         // record miss and costs more than it saves)
@@ -421,8 +448,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
           }
         }
         pk++;
-        if (pk == pend) { in_prim = false; advance = true; }
       }
+      m_scan = __builtin_amdgcn_ballot_w64(pk < pend);  // the lanes whose leaves have primitives left
+      m_up = m_prim & ~m_scan;
       const uint32_t n_tri = (uint32_t)__popcll(__ballot(is_tri));
       c_tri += n_tri;
       c_sph += n_prim - n_tri;
@@ -442,7 +470,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
         IZPI_MARK("spill");
         any_spill = true;
         IZPI_IC(ic_spill);
-        if (busy && !in_prim) {
+        if (lane_of(m_node)) {
           while (sp + 3 - low > S) {
             gsp[(size_t)low * spill_stride] = stk[(low & (S - 1)) * 256];
             low++;
@@ -453,7 +481,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
         }
       }
       IZPI_MARK("node_loads");
-      if (busy && !in_prim) {
+      // (taken over the whole wave: the mask leaves the exec-masked region below as it is)
+      const uint64_t m_inner = __builtin_amdgcn_ballot_w64(cur >= -1);
+      if (lane_of(m_node)) {
         const float tm = (float)tmax;
         // An inner node (4-slot box test) and a leaf's slot-0 re-test (A10) run as ONE
         // code path: a leaf lane's 32-B GLeaf box lands in slot 0 (selects below), its
@@ -553,7 +583,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
         // instead of branches: each divergent branch costs exec-mask and lane-mask
         // bookkeeping on the scalar unit.
         // (a leaf lane has slot 0 only: ch.x is its own ref, never -1)
-        const uint64_t m_inner = __builtin_amdgcn_ballot_w64(cur >= -1);
         const uint64_t b0 = hit[0] & __builtin_amdgcn_ballot_w64(ch.x != -1),
                        b1 = hit[1] & m_inner & __builtin_amdgcn_ballot_w64(ch.y != -1),
                        b2 = hit[2] & m_inner & __builtin_amdgcn_ballot_w64(ch.z != -1),
@@ -566,8 +595,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
         // after its parent re-tests the same f32 box with the same tMax (A10): the result
         // is known to be a hit, so its node load is skipped too (the visit is still counted).
         const bool enter = ref_is_leaf(next) && (is_leaf || sc.leaf_shortcut);
-        leaf_next = enter && !is_leaf;
-        in_prim = enter;
         if constexpr (DIST) {
           lref = enter ? next : lref;
         } else {
@@ -587,10 +614,23 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
         stk[(sp & (S - 1)) * 256] = e0;
         stk[((sp + 1) & (S - 1)) * 256] = e1;
         stk[((sp + 2) & (S - 1)) * 256] = ch.w;
-        if (sp + np_ > 64) atomicOr(err, 1u);  // unreachable: the host rejects BVHs deeper than 64 entries
+        if (sp + np_ > 64) {  // unreachable: the host rejects BVHs deeper than 64 entries
+          IZPI_MARK("overflow");
+          atomicOr(err, 1u);
+        }
         sp += np_;
-        advance = !enter;
       }
+      // The lanes this step sent into a leaf scan it now: after a passed re-test their node was
+      // that leaf; those whose node was an inner one went straight from the parent, a shortcut
+      // (one compare on the mode register and the scalar unit, not a ballot of `enter && !is_leaf`).
+      const uint64_t m_after = DIST ? __builtin_amdgcn_ballot_w64(lref < 0) : __builtin_amdgcn_ballot_w64(pk < pend);
+      const uint64_t n_short = (uint64_t)__popcll(m_after & ~m_prim & m_inner);
+      c_nodes += n_short;
+      c_short += n_short;
+      m_scan = m_after;
+      // (next is -1 on the lanes that entered a leaf, and on those outside the step)
+      m_down = __builtin_amdgcn_ballot_w64(next != -1);
+      m_up = m_node & ~(m_down | (m_after & ~m_prim));
     }
 #ifdef IZPI_TRACE_CLOCKS
     IZPI_CLK(k1); if (clk_prim) k_prim += k1 - k0; else k_node += k1 - k0; k0 = k1;
@@ -598,37 +638,39 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
     // ---- advance: next child, else pop (bvh4.go:150-160), else the ray is done
     {
       IZPI_MARK("advance");
-      const bool do_pop = advance && next == -1 && sp > 0;
-      const bool do_fin = advance && next == -1 && sp == 0;
+      const uint64_t m_pop = m_up & __builtin_amdgcn_ballot_w64(sp > 0), m_fin = m_up & ~m_pop;  // (sp == 0)
+      const bool do_pop = lane_of(m_pop), do_fin = lane_of(m_fin);
       // the LDS read is unconditional (and volatile, so that the compiler keeps it a ds_read:
       // a select of the LDS and spill addresses becomes a flat load, whose wait also
       // drains every store)
       const int spn = sp - 1;
       int32_t top = *(volatile __attribute__((address_space(3))) int32_t*)&lds_stack[threadIdx.x + (spn & (S - 1)) * 256];
 #ifdef IZPI_TRACE_ICOUNT
-      if (__ballot(do_pop) != 0) ic_pop++;
-      if (__ballot(do_fin) != 0) ic_finish++;
+      if (m_pop != 0) ic_pop++;
+      if (m_fin != 0) ic_finish++;
 #endif
-      if (any_spill && __ballot(do_pop && spn < low) != 0) {
-        IZPI_MARK("readback");
-        IZPI_IC(ic_readback);
-        if (do_pop && spn < low) {
-          top = gsp[(size_t)spn * spill_stride];
-          low = spn;
+      if (any_spill) {  // (only a wave that has spilled tests its pops against the spilled range)
+        IZPI_MARK("spilled");
+        IZPI_IC(ic_spilled);
+        if (__ballot(do_pop && spn < low) != 0) {
+          IZPI_MARK("readback");
+          IZPI_IC(ic_readback);
+          if (do_pop && spn < low) {
+            top = gsp[(size_t)spn * spill_stride];
+            low = spn;
 #ifdef IZPI_SHADOW
-          c_spill_ld++;
+            c_spill_ld++;
 #endif
+          }
+          __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) here, not for every pop
         }
-        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) here, not for every pop
       }
       IZPI_MARK("advance_tail");
-      cur = (advance && next != -1) ? next : (do_pop ? top : cur);
-      sp = (advance && next == -1) ? spn : sp;  // a pop, or the ray is done: sp == -1, the lane is idle
+      cur = lane_of(m_down) ? next : (do_pop ? top : cur);
+      sp = lane_of(m_up) ? spn : sp;  // a pop, or the ray is done: sp == -1, the lane is idle
       // An entry pushed after the last accepted hit meets the same tMax it was pushed
       // with, so a leaf's re-test against its (identical) box passes: skip the load.
       const bool lf = do_pop && ref_is_leaf(top) && spn >= clean_from && sc.leaf_shortcut;
-      in_prim = in_prim || lf;
-      leaf_next = leaf_next || lf;
       if constexpr (DIST) {
         lref = lf ? top : lref;
       } else {
@@ -646,13 +688,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
         } else {  // nothing reads (u, v): 16 B per entry (hs == 1)
           sst(wp.in.hit + qi, hit_pack(bprim >= 0 ? tmax : 0.0, bprim));
         }
-        busy = false;
       }
     }
     IZPI_MARK("advance_end");
-    const uint64_t n_short = (uint64_t)__popcll(__builtin_amdgcn_ballot_w64(leaf_next));  // leaf visits taken by a shortcut
-    c_nodes += n_short;
-    c_short += n_short;
 #ifdef IZPI_TRACE_CLOCKS
     IZPI_CLK(k1); k_adv += k1 - k0;
 #endif
@@ -675,7 +713,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
 #ifdef IZPI_TRACE_ICOUNT
   if (lane == 0) {  // (node steps on the fast slab: CNT_NSTEP less the twin's; primitive steps: CNT_PSTEP)
     count_add(wp.cpart, counters, CNT_IC_ITER, ic_iter);
-    count_add(wp.cpart, counters, CNT_IC_IDLE, ic_idle);
+    count_add(wp.cpart, counters, CNT_IC_DUE, ic_due);
+    count_add(wp.cpart, counters, CNT_IC_SPILLED, ic_spilled);
     count_add(wp.cpart, counters, CNT_IC_DEQUEUE, ic_dequeue);
     count_add(wp.cpart, counters, CNT_IC_REFILL, ic_refill);
     count_add(wp.cpart, counters, CNT_IC_TWIN, ic_twin);
@@ -698,7 +737,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
 }
 
 
-// (DIST, TRI, LB, RL, Q) of the compiled instances
+// (DIST, TRI, LB, RL, Q) of the compiled instances; each also with the 32-bit offsets (the
+// global-memory ones) and with the three-primitive leaf bound (the distributed ones): trace_kernel
 #define IZPI_T2_LIST(X)                                                                                           \
   X(true, false, false, false, false) X(true, true, false, false, false) X(false, false, false, false, false)        \
   X(false, true, false, false, false) X(true, false, true, false, false) X(true, true, true, false, false)           \
@@ -708,6 +748,28 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
 // too shallow to fill it, and the 8 KB it frees hold the rays (still 5 blocks per CU).
 constexpr int ring_of(bool lb, bool rl) { return lb && rl ? 8 : TRACE_RING; }
 int trace_ring(const Tracer& t) { return ring_of(t.lds_bvh, t.ray_lds); }
+
+typedef void (*TraceKernel)(const DevScene, const WaveParams, unsigned long long*, uint32_t*, int32_t*, uint32_t, uint32_t,
+                            uint32_t, uint32_t);
+template <bool P, bool T, bool L, bool R, bool Q>
+static TraceKernel trace_instance(bool a32, bool leaf3, bool tmin_fixed) {
+  constexpr int S = ring_of(L, R);
+  // (!L, P: the flags of the combinations that are not compiled fold onto the ones that are)
+  if (a32 && !L) {
+    if (leaf3 && P) return tmin_fixed ? k_trace2<S, TRACE_WPE, P, T, L, R, Q, !L, P, P> : k_trace2<S, TRACE_WPE, P, T, L, R, Q, !L, P, false>;
+    return k_trace2<S, TRACE_WPE, P, T, L, R, Q, !L, false, false>;
+  }
+  if (leaf3 && P) return tmin_fixed ? k_trace2<S, TRACE_WPE, P, T, L, R, Q, false, P, P> : k_trace2<S, TRACE_WPE, P, T, L, R, Q, false, P, false>;
+  return k_trace2<S, TRACE_WPE, P, T, L, R, Q, false, false, false>;
+}
+// The instance a tracer's flags name, or null. tmin_fixed: FT, known at the launch.
+static TraceKernel trace_kernel(const Tracer& t, bool tmin_fixed) {
+#define IZPI_T2_PICK(P, T, L, R, Q) \
+  if (t.p2 == P && t.tri == T && t.lds_bvh == L && t.ray_lds == R && t.qnodes == Q) return trace_instance<P, T, L, R, Q>(t.a32, t.leaf3, tmin_fixed);
+  IZPI_T2_LIST(IZPI_T2_PICK)
+#undef IZPI_T2_PICK
+  return nullptr;
+}
 
 // Pick the k_trace2 instance and its grid (no allocation: the caller grows d_spill to
 // t->spill_bytes).
@@ -735,17 +797,20 @@ int make_tracer(izpi_ctx* ctx, const izpi_render_tuning& tu, bool need_uv, Trace
   // 32-bit record offsets where the uploaded scene allows them (IZPI_TUNE_WIDE_ADDR: the 64-bit
   // addresses of a scene past 4 GiB, for tests)
   t->a32 = ctx->sc.addr32 != 0 && !(tu.flags & IZPI_TUNE_WIDE_ADDR);
+  // the distributed primitive step sized for leaves of at most three primitives where the
+  // uploaded tree has no larger one (IZPI_TUNE_LEAF4: the four-primitive form, for tests)
+  t->leaf3 = t->p2 && ctx->sc.leaf_max <= 3 && !(tu.flags & IZPI_TUNE_LEAF4);
   if (tu.prim_weight) t->prim_w = tu.prim_weight;
   if (tu.trace_chunk) t->tchunk = tu.trace_chunk;
-  if (tu.refill_min) t->refill_min = std::min<uint32_t>(64, tu.refill_min);
-  int rc = IZPI_ERR_INVALID;
-  ctx->err = "no k_trace2 instance for this scene and tuning";
-#define IZPI_T2_OCC(P, T, L, R, Q)                                                               \
-  if (t->p2 == P && t->tri == T && t->lds_bvh == L && t->ray_lds == R && t->qnodes == Q) \
-    rc = t->a32 ? resident_blocks(ctx, k_trace2<ring_of(L, R), TRACE_WPE, P, T, L, R, Q, !L>, &t->blocks)       \
-                : resident_blocks(ctx, k_trace2<ring_of(L, R), TRACE_WPE, P, T, L, R, Q, false>, &t->blocks);
-  IZPI_T2_LIST(IZPI_T2_OCC)
-#undef IZPI_T2_OCC
+  if (tu.refill_min) t->refill_min = std::min<uint32_t>(64, tu.refill_min);  // (1..64: k_trace2's refill test relies on it)
+  // (the grid is sized by the instance without the fixed tMin: the launch's choice changes the
+  // primitive step by a few instructions, not the registers' bound or the LDS)
+  const TraceKernel k = trace_kernel(*t, false);
+  if (!k) {
+    ctx->err = "no k_trace2 instance for this scene and tuning";
+    return IZPI_ERR_INVALID;
+  }
+  const int rc = resident_blocks(ctx, k, &t->blocks);
   if (rc) return rc;
   t->spill_bytes = (size_t)t->blocks * 256 * 64 * sizeof(int32_t);
   return IZPI_OK;
@@ -754,17 +819,8 @@ int make_tracer(izpi_ctx* ctx, const izpi_render_tuning& tu, bool need_uv, Trace
 void launch_trace(izpi_ctx* ctx, const DevScene& sc, const Tracer& t, const WaveParams& wp, hipStream_t st, int32_t* spill) {
   const dim3 g(t.blocks), b(256);
   const uint32_t stride = (uint32_t)t.blocks * 256;
-#define IZPI_T2_LAUNCH(P, T, L, R, Q)                                                                          \
-  if (t.p2 == P && t.tri == T && t.lds_bvh == L && t.ray_lds == R && t.qnodes == Q) {                          \
-    if (t.a32)                                                                                                 \
-      hipLaunchKernelGGL((k_trace2<ring_of(L, R), TRACE_WPE, P, T, L, R, Q, !L>), g, b, 0, st, sc, wp,           \
-                         ctx->d_counters, misc(ctx, 1), spill, stride, t.prim_w, t.tchunk, t.refill_min);       \
-    else                                                                                                       \
-      hipLaunchKernelGGL((k_trace2<ring_of(L, R), TRACE_WPE, P, T, L, R, Q, false>), g, b, 0, st, sc, wp,        \
-                         ctx->d_counters, misc(ctx, 1), spill, stride, t.prim_w, t.tchunk, t.refill_min);       \
-    return;                                                                                                    \
-  }
-  IZPI_T2_LIST(IZPI_T2_LAUNCH)
-#undef IZPI_T2_LAUNCH
+  const bool tmin_fixed = sc.no_pathlen != 0 && wp.in.tminmax == nullptr;
+  hipLaunchKernelGGL(trace_kernel(t, tmin_fixed), g, b, 0, st, sc, wp, ctx->d_counters, misc(ctx, 1), spill, stride, t.prim_w, t.tchunk,
+                     t.refill_min);
 }
 

@@ -1,14 +1,17 @@
 #!/usr/bin/env python3
 """Static instruction counts of one k_trace2 instance, per section of its loop (gfx950, compile only).
 
-    python tools/step_counts.py [--instance 16,5,true,true,false,true,false,true] [--keep DIR] [--trips FILE]
+    python tools/step_counts.py [--instance 16,5,true,true,false,true,false,true,true,true] [--keep DIR] [--trips FILE]
                                 [--sq VALU,SALU,BRANCH] [extra hipcc flags...]
 
 trace.hip is compiled device-only to assembly twice: as the product builds it, and with
 -DIZPI_STEP_MARKS, which puts a comment marker (no instruction) at the head of each section
-of the loop: head (idle ballot), idle (an iteration with idle lanes), dequeue, refill, pick (step choice), prim, node (step
+of the loop: head (idle ballot and the one test for a refill, a dequeue or the exit), due (an iteration in which that
+test passes), dequeue, refill, pick (step choice), prim, node (step
 counters and the ring-full test), spill, node_loads, slab_fast, slab_twin, node_tail,
-advance (the pop candidate's read), readback, advance_tail, finish, advance_end.
+advance (the pop candidate's read), spilled (a wave that has spilled tests its pops against the
+spilled range), readback, advance_tail, finish, advance_end; overflow (the stack-depth error of the node
+step, which no uploaded tree reaches: no trips).
 The marked kernel is split into its basic blocks (labels, the compiler's `; %bb.N:` notes,
 branches). A block outside the loop (the `in Loop` / `Parent Loop` notes say which are inside)
 goes to the row `(entry)` before the loop's header and `(epilogue)` after it: the counter
@@ -88,11 +91,11 @@ def kernel_text(asm, prefix):
 
 
 # the trip count (a key of the IZPI_TRACE_ICOUNT line, or a sum of keys) of each row
-TRIPS = {"(entry)": ["waves"], "(epilogue)": ["waves"], "(cold loops)": ["spill"], "head": ["iterations"], "idle": ["idle"],
+TRIPS = {"(entry)": ["waves"], "(epilogue)": ["waves"], "(cold loops)": ["spill"], "head": ["iterations"], "due": ["due"],
          "dequeue": ["dequeue"], "refill": ["refill"], "pick": ["iterations"], "prim": ["prim"],
          "node": ["node_fast", "node_twin"], "spill": ["spill"], "node_loads": ["node_fast", "node_twin"],
          "slab_fast": ["node_fast"], "slab_twin": ["node_twin"], "node_tail": ["node_fast", "node_twin"],
-         "advance": ["iterations"], "readback": ["readback"], "advance_tail": ["iterations"], "finish": ["finish"],
+         "advance": ["iterations"], "spilled": ["spilled"], "overflow": [], "readback": ["readback"], "advance_tail": ["iterations"], "finish": ["finish"],
          "advance_end": ["iterations"]}
 
 
@@ -201,7 +204,7 @@ def compile_asm(out, extra):
 
 def main():
     argv = sys.argv[1:]
-    inst = "16,5,true,true,false,true,false,true"
+    inst = "16,5,true,true,false,true,false,true,true,true"
     keep = trips = sq = None
     while argv and argv[0] in ("--instance", "--keep", "--trips", "--sq"):
         if argv[0] == "--instance":
