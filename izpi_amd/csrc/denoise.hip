@@ -8,7 +8,7 @@
 // the Infinity Cache, which holds the four canvases of a 1024 x 1024 frame) and writes
 // C_{i+1}; iterations ping-pong between the caller's output and one scratch canvas the
 // context keeps, so that the last one lands in the output.
-#include "izpi_kern.h"
+#include "izpi_runtime.h"
 
 #include "denoise.h"
 

@@ -13,7 +13,7 @@
 namespace izd {
 
 // The scene as the kernels read it (izpi_gpu_upload_scene). The small tables k_shade / k_tail
-// stage per block in LDS are laid out by izpi_gpu.hip's lds_off (compile-time offsets; a
+// stage per block in LDS are laid out by izpi_kern.h's lds_off (compile-time offsets; a
 // render sizes the arena to the prefix it stages, lds_bytes).
 struct DevScene {
   const GInner* inner;

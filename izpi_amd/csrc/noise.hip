@@ -4,7 +4,7 @@
 // with the host twin (noise_host.cpp), so both give the same bits. The second moments both
 // read are folded by k_accumulate's moments instance (wavefront.hip). A translation unit of
 // its own, so the other units compile what they compiled before.
-#include "izpi_kern.h"
+#include "izpi_runtime.h"
 #include "noise.h"
 
 namespace {

@@ -1,8 +1,8 @@
 // preview.hip — the Normal, Albedo and WireFrame samplers (sampler/normal.go:28-34,
 // albedo.go:30-36, wireframe.go:34-40) under render/rgb.go:27-41's pixel loop: k_preview_start,
-// k_preview and the batch loop that drives them with k_trace2 (run_preview, izpi_kern.h). A
+// k_preview and the batch loop that drives them with k_trace2 (run_preview, izpi_runtime.h). A
 // translation unit of its own, so the four shade_*.hip units compile what they compiled before.
-#include "izpi_kern.h"
+#include "izpi_runtime.h"
 
 namespace {
 

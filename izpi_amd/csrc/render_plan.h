@@ -12,7 +12,7 @@
 namespace izpi_internal {
 
 // The sizes of the device records the plan counts, pinned against the real types where those
-// are declared (izpi_gpu.hip).
+// are declared (izpi_runtime.h).
 namespace plan_size {
 constexpr uint64_t RAY = 48;        // RayOD
 constexpr uint64_t PATH_HOT = 16;   // PathHot

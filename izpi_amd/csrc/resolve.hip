@@ -3,7 +3,7 @@
 // the sums of a one-shot render (shade.h), without consuming them: divide by the samples done
 // and write the pixel, packed or into the canvas. A translation unit of its own, so the
 // shading units compile what they compiled before.
-#include "izpi_kern.h"
+#include "izpi_runtime.h"
 
 // One thread per pixel in packed order: 24 B of sums in, 32 B out; HBM-streaming. The sums
 // are read only.

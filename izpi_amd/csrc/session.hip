@@ -1,0 +1,282 @@
+// session.hip — progressive sessions on one context (izpi_gpu_progressive_*): the samples of a
+// request in resumable steps, snapshots of the running sums, the noise estimate and its stop
+// rule (noise.h). A device group's session (multi.hip) is one of these per device.
+#include "izpi_runtime.h"
+#include "noise.h"
+
+namespace izpi_internal {
+// The library's own copy of a session's request and of the arrays it points to.
+int session_copy_request(izpi_ctx::Session& ss, const izpi_render_req* req, std::string& err) {
+  ss = izpi_ctx::Session{};
+  ss.req = request_copy(req);
+  ss.tuning = tuning_of(req);
+  ss.req.tuning = req->tuning ? &ss.tuning : nullptr;
+  if (ss.req.num_tiles) {
+    if (!ss.req.tiles) { err = "num_tiles without tiles"; return IZPI_ERR_INVALID; }
+    ss.tiles.assign(ss.req.tiles, ss.req.tiles + 4 * (size_t)ss.req.num_tiles);
+    ss.req.tiles = ss.tiles.data();
+  }
+  if (ss.req.num_bg_spd) {
+    if (!ss.req.bg_spd_wavelengths || !ss.req.bg_spd_values) { err = "num_bg_spd without the SPD arrays"; return IZPI_ERR_INVALID; }
+    ss.bg_wl.assign(ss.req.bg_spd_wavelengths, ss.req.bg_spd_wavelengths + ss.req.num_bg_spd);
+    ss.bg_val.assign(ss.req.bg_spd_values, ss.req.bg_spd_values + ss.req.num_bg_spd);
+    ss.req.bg_spd_wavelengths = ss.bg_wl.data();
+    ss.req.bg_spd_values = ss.bg_val.data();
+  }
+  return IZPI_OK;
+}
+
+void session_drop(izpi_ctx* ctx) {
+  ctx->session = izpi_ctx::Session{};
+  ctx->prog_done.store(0, std::memory_order_relaxed);
+  ctx->prog_total.store(0, std::memory_order_relaxed);
+}
+
+static int session_zero_moments(izpi_ctx* ctx) {
+  izpi_ctx::Session& ss = ctx->session;
+  const size_t bytes = (size_t)ss.num_pixels * 3 * sizeof(double);
+  const int rc = grow(ctx, (void**)&ctx->d_moments, &ctx->moments_cap, bytes);
+  if (rc) return rc;
+  HIP_TRY(hipMemsetAsync(ctx->d_moments, 0, bytes, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  ss.noise = true;
+  return IZPI_OK;
+}
+
+// begin: render_body's own checks, plan and allocation for a request of step_spp samples
+// (its prepare_only form, which for a session also zeroes the sums and the counters).
+// With IZPI_PROG_NOISE the samples' second moments start at zero in a buffer of their own
+// (24 B per pixel; it only grows, and no workspace plan counts it).
+int session_begin(izpi_ctx* ctx, const izpi_render_req* req, uint32_t step_spp, uint32_t flags) {
+  if (ctx->session.open) { ctx->err = "a progressive session is already open"; return IZPI_ERR_INVALID; }
+  if (!req || step_spp == 0) { ctx->err = "progressive_begin: a request and step_spp >= 1"; return IZPI_ERR_INVALID; }
+  if (flags & ~(uint32_t)IZPI_PROG_NOISE) { ctx->err = "progressive_begin: unknown flags"; return IZPI_ERR_INVALID; }
+  izpi_ctx::Session& ss = ctx->session;
+  int rc = session_copy_request(ss, req, ctx->err);
+  if (!rc) {
+    ss.step_spp = std::min(step_spp, std::max(1u, ss.req.spp));
+    rc = render_body(ctx, &ss.req, RenderCall{SampleRange{0, 0, true}, ss.step_spp, true}, nullptr);
+  }
+  if (!rc && (flags & IZPI_PROG_NOISE)) rc = session_zero_moments(ctx);
+  if (rc) {
+    const std::string why = ctx->err;
+    session_drop(ctx);
+    ctx->err = why;
+    return rc;
+  }
+  ss.cum = izpi_render_stats{};
+  ss.open = true;
+  ctx->prog_done.store(0, std::memory_order_relaxed);
+  ctx->prog_total.store((uint64_t)ss.num_pixels * ss.req.spp, std::memory_order_relaxed);
+  return IZPI_OK;
+}
+
+static int session_usable(izpi_ctx* ctx) {
+  if (!ctx->session.open) { ctx->err = "no progressive session is open"; return IZPI_ERR_INVALID; }
+  if (ctx->session.broken) { ctx->err = "the session's last step failed: end it"; return IZPI_ERR_INVALID; }
+  return IZPI_OK;
+}
+
+// step: samples [done, done + n) through render_body's chunk loops, never finalised. The
+// device counters run on from step to step; times and launches are summed here.
+int session_step(izpi_ctx* ctx, uint32_t spp, izpi_render_stats* stats) {
+  int rc = session_usable(ctx);
+  if (rc) return rc;
+  izpi_ctx::Session& ss = ctx->session;
+  const uint32_t n = std::min(spp ? spp : ss.step_spp, ss.req.spp - ss.done);
+  if (n) {
+    rc = render_body(ctx, &ss.req, RenderCall{SampleRange{ss.done, ss.done + n, true}, ss.step_spp, false}, nullptr);
+    if (rc) {  // a chunk may or may not be in the sums
+      ss.broken = true;
+      return rc;
+    }
+    ss.done += n;
+    izpi_render_stats s = ctx->last;
+    s.kernel_ms += ss.cum.kernel_ms; s.shade_ms += ss.cum.shade_ms; s.tail_ms += ss.cum.tail_ms;
+    s.total_ms += ss.cum.total_ms; s.alloc_ms += ss.cum.alloc_ms; s.launches += ss.cum.launches;
+    ss.cum = s;
+    ctx->last = s;
+    ctx->prog_done.store((uint64_t)ss.num_pixels * ss.done, std::memory_order_relaxed);
+  }
+  if (stats) *stats = ss.cum;
+  return IZPI_OK;
+}
+
+// The session's tiles on the device (izpi_gpu_unpack_tiles may have used d_tiles since the last step).
+static int session_tiles(izpi_ctx* ctx) {
+  const izpi_ctx::Session& ss = ctx->session;
+  const int rc = grow(ctx, (void**)&ctx->d_tiles, &ctx->tiles_cap, ss.run_tiles.size() * sizeof(uint32_t));
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(ctx->d_tiles, ss.run_tiles.data(), ss.run_tiles.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+  return IZPI_OK;
+}
+
+// The noise estimate needs a session begun with IZPI_PROG_NOISE and two samples (n - 1 divides;
+// need = 0: a converge, which steps before it estimates). True, with the message, when it lacks one.
+bool session_lacks_noise(const izpi_ctx::Session& ss, std::string& err, uint32_t need) {
+  if (!ss.noise) { err = "noise: the session was begun without IZPI_PROG_NOISE"; return true; }
+  if (ss.done < need) { err = "noise: needs at least 2 samples"; return true; }
+  return false;
+}
+// The caller's parameters, or the defaults for a null pointer, checked (nz::check_params).
+bool noise_params_ok(const izpi_noise_params* params, izpi_noise_params& p, std::string& err) {
+  p = params ? *params : nz::defaults();
+  const char* bad = nz::check_params(p);
+  if (bad) err = bad;
+  return !bad;
+}
+// A snapshot's form is known, and the session has a sample to show.
+bool snapshot_form_ok(uint32_t form, uint32_t done, std::string& err) {
+  if (form != IZPI_SNAP_CANVAS && form != IZPI_SNAP_DISPLAY && form != IZPI_SNAP_NOISE) { err = "unknown snapshot form"; return false; }
+  if (done == 0) { err = "snapshot before the session's first sample"; return false; }
+  return true;
+}
+static NoiseParams noise_params(izpi_ctx* ctx) {
+  const izpi_ctx::Session& ss = ctx->session;
+  NoiseParams np{};
+  np.num_pixels = ss.num_pixels; np.done = ss.done; np.width = ss.req.width; np.height = ss.req.height;
+  np.tile_w = ss.tile_w; np.tile_h = ss.tile_h; np.sampler = ss.req.sampler; np.out_layout = ss.req.out_layout;
+  np.threshold = IZPI_NOISE_DEFAULT_THRESHOLD; np.floor = IZPI_NOISE_DEFAULT_FLOOR;
+  np.tiles = ctx->d_tiles; np.running = ctx->d_running; np.moments = ctx->d_moments;
+  return np;
+}
+
+// noise: k_noise_stats over the sums and moments; the block sums are added here, in block order.
+int session_noise(izpi_ctx* ctx, const izpi_noise_params* params, izpi_noise_stats* out) {
+  int rc = session_usable(ctx);
+  if (rc) return rc;
+  izpi_noise_params p;
+  const izpi_ctx::Session& ss = ctx->session;
+  if (!noise_params_ok(params, p, ctx->err) || session_lacks_noise(ss, ctx->err)) return IZPI_ERR_INVALID;
+  hipStream_t st = ctx->stream;
+  if ((rc = session_tiles(ctx))) return rc;
+  const size_t blocks = ((size_t)ss.num_pixels + nz::BLOCK - 1) / nz::BLOCK;
+  if ((rc = grow(ctx, (void**)&ctx->d_noisepart, &ctx->noisepart_cap, 5 * blocks * sizeof(double)))) return rc;
+  NoiseParams np = noise_params(ctx);
+  np.threshold = p.threshold; np.floor = p.floor;
+  np.block_sums = ctx->d_noisepart;
+  np.block_counts = (unsigned long long*)(ctx->d_noisepart + blocks);
+  HIP_TRY(hipEventRecord(ctx->ev0, st));
+  launch_noise_stats(st, np);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(ctx->ev1, st));
+  std::vector<double> part(5 * blocks);
+  HIP_TRY(hipMemcpyAsync(part.data(), ctx->d_noisepart, part.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  float ms = 0;
+  HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+  izpi_noise_stats s{};
+  unsigned long long max_bits = 0;
+  for (size_t b = 0; b < blocks; b++) {  // (every block writes its partials: nothing to zero)
+    unsigned long long cnt[4];
+    memcpy(cnt, part.data() + blocks + 4 * b, sizeof(cnt));
+    s.pixels += cnt[0]; s.nonfinite += cnt[1]; s.above += cnt[2];
+    max_bits = std::max(max_bits, cnt[3]);
+    s.sum_error = s.sum_error + part[b];
+  }
+  s.max_error = gm::from_bits(max_bits);
+  s.device_ms = ms;
+  s.done = ss.done;
+  s.converged = nz::converged(s.pixels, s.nonfinite, s.above, s.done, p);
+  if (out) *out = s;
+  return IZPI_OK;
+}
+
+// snapshot: k_resolve of the sums into device memory, then (IZPI_SNAP_CANVAS) the request's post.
+int session_snapshot(izpi_ctx* ctx, uint32_t form, double* out_dev) {
+  int rc = session_usable(ctx);
+  if (rc) return rc;
+  const izpi_ctx::Session& ss = ctx->session;
+  if (!snapshot_form_ok(form, ss.done, ctx->err)) return IZPI_ERR_INVALID;
+  if (form == IZPI_SNAP_NOISE && session_lacks_noise(ss, ctx->err)) return IZPI_ERR_INVALID;
+  if (!out_dev) { ctx->err = "null output"; return IZPI_ERR_INVALID; }
+  hipStream_t st = ctx->stream;
+  if ((rc = session_tiles(ctx))) return rc;
+  if (form == IZPI_SNAP_NOISE) {  // k_noise_resolve: the standard errors, where k_resolve writes the pixels; no post
+    NoiseParams np = noise_params(ctx);
+    np.out = out_dev;
+    launch_noise_resolve(st, np);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    return IZPI_OK;
+  }
+  ResolveParams rp{};
+  rp.num_pixels = ss.num_pixels; rp.done = ss.done; rp.width = ss.req.width; rp.height = ss.req.height;
+  rp.tile_w = ss.tile_w; rp.tile_h = ss.tile_h; rp.sampler = ss.req.sampler; rp.out_layout = ss.req.out_layout;
+  rp.form = form; rp.exposure = ss.req.exposure;
+  rp.tiles = ctx->d_tiles; rp.running = ctx->d_running; rp.out = out_dev;
+  launch_resolve(st, rp);
+  HIP_TRY(hipGetLastError());
+  if (form == IZPI_SNAP_CANVAS && (rc = apply_post(ctx, &ss.req, out_dev))) return rc;
+  HIP_TRY(hipStreamSynchronize(st));
+  return IZPI_OK;
+}
+
+}  // namespace izpi_internal
+
+using namespace izpi_internal;
+
+extern "C" {
+
+int izpi_gpu_progressive_begin_ex(izpi_ctx* ctx, const izpi_render_req* req, uint32_t step_spp, uint32_t flags) {
+  if (!ctx) return IZPI_ERR_INVALID;
+  HIP_TRY(hipSetDevice(ctx->device));
+  return session_begin(ctx, req, step_spp, flags);
+}
+
+int izpi_gpu_progressive_begin(izpi_ctx* ctx, const izpi_render_req* req, uint32_t step_spp) {
+  return izpi_gpu_progressive_begin_ex(ctx, req, step_spp, 0);
+}
+
+int izpi_gpu_progressive_noise(izpi_ctx* ctx, const izpi_noise_params* p, izpi_noise_stats* out) {
+  if (!ctx) return IZPI_ERR_INVALID;
+  HIP_TRY(hipSetDevice(ctx->device));
+  return session_noise(ctx, p, out);
+}
+
+int izpi_gpu_progressive_converge(izpi_ctx* ctx, const izpi_noise_params* p, izpi_render_stats* stats, izpi_noise_stats* noise) {
+  if (!ctx) return IZPI_ERR_INVALID;
+  int rc = session_usable(ctx);
+  if (rc) return rc;
+  izpi_noise_params q;
+  if (!noise_params_ok(p, q, ctx->err) || session_lacks_noise(ctx->session, ctx->err, 0)) return IZPI_ERR_INVALID;
+  HIP_TRY(hipSetDevice(ctx->device));
+  rc = converge_loop(q, ctx->session.req.spp, [&]() { return session_step(ctx, 0, nullptr); },
+                     [&](const izpi_noise_params& np, izpi_noise_stats* ns) { return session_noise(ctx, &np, ns); },
+                     [&]() { return ctx->session.done; }, noise);
+  if (stats) *stats = ctx->session.cum;
+  return rc;
+}
+
+int izpi_gpu_progressive_step(izpi_ctx* ctx, uint32_t spp, izpi_render_stats* stats) {
+  if (!ctx) return IZPI_ERR_INVALID;
+  HIP_TRY(hipSetDevice(ctx->device));
+  return session_step(ctx, spp, stats);
+}
+
+int izpi_gpu_progressive_snapshot_device(izpi_ctx* ctx, uint32_t form, double* out_dev) {
+  if (!ctx) return IZPI_ERR_INVALID;
+  HIP_TRY(hipSetDevice(ctx->device));
+  return session_snapshot(ctx, form, out_dev);
+}
+
+int izpi_gpu_progressive_snapshot(izpi_ctx* ctx, uint32_t form, double* out_host) {
+  if (!ctx) return IZPI_ERR_INVALID;
+  if (!out_host) { ctx->err = "null output"; return IZPI_ERR_INVALID; }
+  int rc = session_usable(ctx);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(ctx->device));
+  const size_t bytes = izpi_gpu_output_bytes(&ctx->session.req);
+  if ((rc = output_from_host(ctx, out_host, bytes))) return rc;
+  if ((rc = session_snapshot(ctx, form, ctx->d_out))) return rc;
+  return output_to_host(ctx, out_host, bytes);
+}
+
+int izpi_gpu_progressive_end(izpi_ctx* ctx) {
+  if (!ctx) return IZPI_ERR_INVALID;
+  if (!ctx->session.open) { ctx->err = "no progressive session is open"; return IZPI_ERR_INVALID; }
+  session_drop(ctx);
+  return IZPI_OK;
+}
+
+}  // extern "C"

@@ -1,6 +1,6 @@
 // trace.hip — BVH4.Hit (hitable/bvh4.go:49-164) as the wavefront's traversal kernel k_trace2,
-// and the host's choice of its instance (izpi_kern.h).
-#include "izpi_kern.h"
+// and the host's choice of its instance (izpi_runtime.h).
+#include "izpi_runtime.h"
 
 // BVH4.Hit, step-scheduled variant. Each lane is in one of two modes: NODE (visit
 // the node `cur`: the 4-slot box test of an inner node, or the slot-0 re-test of a

@@ -4,7 +4,7 @@
 // a table of kernel pointers (ShadeKernels, filled by the shade_*.hip units); and the small
 // kernels of the loop that depend on no instance: the forward refill's plans, the overflow
 // pool's rings, the ordered per-pixel sums (k_accumulate, which the preview samplers share).
-#include "izpi_kern.h"
+#include "izpi_runtime.h"
 #include "noise.h"
 
 #include <type_traits>

@@ -15,7 +15,7 @@ import pytest
 
 from izpi_amd import _native as N
 from izpi_amd import configs
-from izpi_amd.renderer import GPURenderer, MultiGPURenderer
+from izpi_amd.renderer import GPURenderer, MultiGPURenderer, make_request
 from oracle import oracle as O
 from tests import preview_ref as PR
 from tests.test_forward_accumulation import CASES, scene_case
@@ -243,6 +243,69 @@ def test_session_rules(gpu):
         s.step()
     assert_bitwise(r.render(), ref, r.stats, ref_stats)
     r.close()
+
+
+def test_multi_session_rules(gpu):
+    """What a device group's session refuses: the status and the exact izpi_gpu_multi_last_error
+    text of each call, on two contexts of device 0 and one 16x16 frame."""
+    scene = scene_of("cornell")[0]
+    L = N.lib()
+    m = MultiGPURenderer(scene, 16, 16, 4, [0, 0], bvh="reference")
+    req = make_request(16, 16, 4, m.max_depth, m.sampler, m.background, m.seed, m.exposure)
+    canvas = np.zeros((16, 16, 4))
+    ptr = canvas.ctypes.data_as(C.c_void_p)
+    st = (N.RenderStats * 2)()
+    ns = N.NoiseStats()
+    bad = N.noise_params(threshold=0.0)  # nz::check_params' first rule
+
+    def refused(rc, text):
+        assert rc == N.IZPI_ERR_INVALID
+        assert L.izpi_gpu_multi_last_error(m.m).decode() == text
+
+    # no session is open
+    closed = "no progressive session is open"
+    refused(L.izpi_gpu_multi_progressive_step(m.m, 1, st), closed)
+    refused(L.izpi_gpu_multi_progressive_snapshot(m.m, N.SNAP_CANVAS, ptr), closed)
+    refused(L.izpi_gpu_multi_progressive_noise(m.m, None, C.byref(ns)), closed)
+    refused(L.izpi_gpu_multi_progressive_converge(m.m, None, st, C.byref(ns)), closed)
+    refused(L.izpi_gpu_multi_progressive_end(m.m), closed)
+    # begin
+    refused(L.izpi_gpu_multi_progressive_begin(m.m, C.byref(req), 0), "progressive_begin: a request and step_spp >= 1")
+    refused(L.izpi_gpu_multi_progressive_begin_ex(m.m, C.byref(req), 2, 2), "progressive_begin: unknown flags")
+    refused(L.izpi_gpu_multi_progressive_end(m.m), closed)  # (neither opened one)
+    # a session begun without IZPI_PROG_NOISE
+    with m.progressive(2) as s:
+        refused(L.izpi_gpu_multi_progressive_begin(m.m, C.byref(req), 2), "a progressive session is already open")
+        refused(L.izpi_gpu_multi_render(m.m, C.byref(req), ptr, st), "a progressive session is open")
+        refused(L.izpi_gpu_multi_prepare(m.m, C.byref(req)), "a progressive session is open")
+        refused(L.izpi_gpu_multi_progressive_snapshot(m.m, 7, ptr), "unknown snapshot form")
+        first = "snapshot before the session's first sample"
+        refused(L.izpi_gpu_multi_progressive_snapshot(m.m, N.SNAP_CANVAS, ptr), first)
+        refused(L.izpi_gpu_multi_progressive_snapshot(m.m, N.SNAP_NOISE, ptr), first)  # (before the noise rules)
+        assert s.step() == 2
+        without = "noise: the session was begun without IZPI_PROG_NOISE"
+        refused(L.izpi_gpu_multi_progressive_noise(m.m, None, C.byref(ns)), without)
+        refused(L.izpi_gpu_multi_progressive_snapshot(m.m, N.SNAP_NOISE, ptr), without)
+        refused(L.izpi_gpu_multi_progressive_converge(m.m, None, st, C.byref(ns)), without)
+        # (the parameters come before the session's noise rules)
+        refused(L.izpi_gpu_multi_progressive_noise(m.m, C.byref(bad), C.byref(ns)),
+                "noise: threshold must be finite and greater than 0")
+        assert not canvas.any()
+        assert s.done == 2 and m.progress() == (16 * 16 * 2, 16 * 16 * 4)  # the session is intact
+        assert s.snapshot().any()
+    # a session begun with it
+    with m.progressive(1, noise=True) as s:
+        assert s.step() == 1
+        few = "noise: needs at least 2 samples"
+        refused(L.izpi_gpu_multi_progressive_noise(m.m, None, C.byref(ns)), few)
+        refused(L.izpi_gpu_multi_progressive_snapshot(m.m, N.SNAP_NOISE, ptr), few)
+        refused(L.izpi_gpu_multi_progressive_converge(m.m, C.byref(bad), st, C.byref(ns)),
+                "noise: threshold must be finite and greater than 0")
+        assert s.done == 1 and m.progress() == (16 * 16, 16 * 16 * 4)
+        assert s.step() == 2
+        assert s.noise()["done"] == 2
+    refused(L.izpi_gpu_multi_progressive_end(m.m), closed)
+    m.close()
 
 
 # ---- 9. multi-GPU

@@ -1,6 +1,6 @@
 """The share plan on CPU: izpi_host_share_units (the units a frame's tiles are dealt in)
 against an independent numpy restatement, and izpi_host_share_tiles' deal of those units.
-The device deals with the same functions (make_shares in izpi_gpu.hip); the GPU tests tie
+The device deals with the same functions (make_shares in multi.hip); the GPU tests tie
 each device's sample count to this plan."""
 import numpy as np
 import pytest

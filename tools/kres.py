@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Per-kernel register / spill / LDS table of izpi_gpu.hip for gfx950 (compile-time remarks).
+"""Per-kernel register / spill / LDS table of one HIP unit for gfx950 (compile-time remarks):
+trace.hip (k_trace2) by default, KRES_SRC=izpi_amd/csrc/shade_colour_fwd.hip for a shading unit.
 
     python tools/kres.py [extra hipcc flags...]
 """
@@ -8,7 +9,7 @@ import re
 import subprocess
 import sys
 
-SRC = os.environ.get("KRES_SRC", "izpi_amd/csrc/izpi_gpu.hip")
+SRC = os.environ.get("KRES_SRC", "izpi_amd/csrc/trace.hip")
 cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
        "-Iinclude", "--cuda-device-only", "-c", "-o", "/tmp/kres.o", SRC, "-Rpass-analysis=kernel-resource-usage"] + sys.argv[1:]
 out = subprocess.run(cmd, capture_output=True, text=True).stderr
