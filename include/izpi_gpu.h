@@ -484,7 +484,8 @@ int izpi_gpu_multi_progressive_end(izpi_multi* m);
  * 2 spp to 0.82 at 4 before it falls): min_spp keeps a frame from "converging" on such an
  * estimate, so do not set it to 2 without a reason.
  *
- *  begin_ex   _begin with flags: IZPI_PROG_NOISE or 0 (any other bit: IZPI_ERR_INVALID).
+ *  begin_ex   _begin with flags: IZPI_PROG_NOISE, with or without IZPI_PROG_ADAPTIVE (below), or 0
+ *             (any other bit, the flag value 2 among them: IZPI_ERR_INVALID).
  *             _begin is _begin_ex(..., 0).
  *  snapshot   IZPI_SNAP_NOISE (every snapshot entry): (se_0, se_1, se_2, 1.0) per pixel in the
  *             session's layout, by IZPI_SNAP_CANVAS's row and tile rule, without req->post;
@@ -524,6 +525,62 @@ int izpi_gpu_multi_progressive_begin_ex(izpi_multi* m, const izpi_render_req* re
 int izpi_gpu_multi_progressive_noise(izpi_multi* m, const izpi_noise_params* p, izpi_noise_stats* out);
 int izpi_gpu_multi_progressive_converge(izpi_multi* m, const izpi_noise_params* p, izpi_render_stats* stats,
                                         izpi_noise_stats* noise);
+
+/* ---- Adaptive sampling of a progressive session (deviation A26) ----
+ * A session begun with IZPI_PROG_NOISE | IZPI_PROG_ADAPTIVE stops sampling the pixels whose
+ * noise estimate has fallen to the threshold. The project's own rule, like the estimate: no
+ * entry above computes it unasked. Sample s of pixel (x, y) draws from its own stream, and sums
+ * and moments fold in sample order, so a pixel's value after n samples depends on that pixel and
+ * n alone: EVERY PIXEL OF AN ADAPTIVE FRAME IS, BIT FOR BIT, THE PIXEL OF A PLAIN RENDER AT THAT
+ * PIXEL'S OWN SAMPLE COUNT n_p, and the counts follow the rule below.
+ *
+ * The session keeps n_p (uint32) per pixel and an active set; every pixel starts active with
+ * n_p = 0 (a buffer of the context's own that only grows; no workspace plan counts it).
+ *   step    renders samples [done, done + k') of the ACTIVE pixels only, k' = min(k, N - done),
+ *           folds them in sample order and adds k' to their n_p. Retirement is final, so every
+ *           active pixel has n_p == done. With no active pixel a step renders nothing and
+ *           leaves done as it is.
+ *   adapt   (done >= 2, else IZPI_ERR_INVALID; p == NULL: the defaults, checked as _noise checks
+ *           them) evaluates every active pixel by the rule above at n = done. The pixel STAYS
+ *           ACTIVE iff it is counted (sample row y >= 1), finite and e > threshold; every other
+ *           pixel retires for good with n_p = done. Uncounted pixels never reach a canvas and
+ *           non-finite ones can never converge: both retire at the first evaluation. tolerated
+ *           and min_spp do not bear on a retirement. out (may be NULL): pixels and nonfinite as
+ *           _noise counts them, active after this call, retired by this call, samples = the sum
+ *           of n_p over the session's pixels, device_ms of the call's kernels, done, and
+ *           converged = done >= min_spp && (double)active <= tolerated * (double)(pixels -
+ *           nonfinite).
+ *   converge  on an adaptive session: step(step_spp), then adapt once done >= max(2, min_spp),
+ *           until adapt reports converged or done == N. Integers only: every share plan stops
+ *           alike. A session in which no pixel is active (an earlier adapt, legal from done >= 2
+ *           whatever min_spp is, retired them all) has nothing left to render: converge returns
+ *           at once with done as it is. noise (may be NULL) is _noise's statistic of the frame
+ *           as the call leaves it, when the call made an adapt or found no active pixel (else
+ *           noise->done == 0); its converged is _noise's, so 0 while done < min_spp.
+ *   snapshot, noise  use n_p wherever they used done (the mean, the standard errors, e). A
+ *           retired pixel's sums no longer change, so noise's above equals adapt's active.
+ *           IZPI_SNAP_SAMPLES writes (n_p, n_p, n_p, 1.0) as doubles by IZPI_SNAP_CANVAS's row and
+ *           tile rule, without req->post: the sample-count map. IZPI_ERR_INVALID on a session
+ *           that is not adaptive.
+ * The counters are additive per sample: they equal the sum, over the steps, of a plain render
+ * of exactly the samples each step rendered. stats->samples is the sum of n_p, and
+ * izpi_gpu_progress reports it against pixels * N. Until the first retirement (adapt never
+ * called, or nothing retired yet) the session runs the plain session's kernels: its sums,
+ * moments, counters and CANVAS / DISPLAY / NOISE snapshots are those of a session begun with
+ * IZPI_PROG_NOISE alone, bit for bit.
+ * IZPI_PROG_ADAPTIVE without IZPI_PROG_NOISE, or with a preview sampler (one ray per sample: not
+ * worth adapting), is IZPI_ERR_INVALID. The multi form: every device adapts its own share (the
+ * rule is per pixel, so the image and the map are one device's); the integers are added and
+ * device_ms is the largest. izpi_host_adapt (izpi_host.h) is the twin on the host. */
+enum { IZPI_PROG_ADAPTIVE = 4 };  /* with IZPI_PROG_NOISE; the flag value 2 stays unknown: callers were promised that the flag words 2 and 3 are refused */
+enum { IZPI_SNAP_SAMPLES = 3 };   /* with IZPI_SNAP_CANVAS, IZPI_SNAP_DISPLAY, IZPI_SNAP_NOISE */
+typedef struct izpi_adapt_stats {
+  uint64_t pixels, nonfinite, active, retired, samples;
+  double device_ms;
+  uint32_t done, converged;
+} izpi_adapt_stats;
+int izpi_gpu_progressive_adapt(izpi_ctx* ctx, const izpi_noise_params* p, izpi_adapt_stats* out);
+int izpi_gpu_multi_progressive_adapt(izpi_multi* m, const izpi_noise_params* p, izpi_adapt_stats* out);
 
 /* Bytes of device output izpi_gpu_render_device writes for `req`. */
 uint64_t izpi_gpu_output_bytes(const izpi_render_req* req);

@@ -188,11 +188,24 @@ int izpi_host_denoise(const double* colour, const double* normal, const double* 
 int izpi_host_noise(const double* sums, const double* moment2, const uint8_t* counted, uint32_t num_pixels, uint32_t done,
                     uint32_t sampler, const izpi_noise_params* p, double* se_out, izpi_noise_stats* out);
 
+/* The host twin of izpi_gpu_progressive_adapt (izpi_gpu.h states the rule; noise.h's arithmetic):
+ * one evaluation over a session's pixels in packed order. sums, moment2: [num_pixels][3];
+ * counted[p] != 0 marks the counted pixels (NULL: all); samples[p]: n_p (read only: an active
+ * pixel has n_p == done, a retired one what it retired with); active[p] != 0 on entry marks the
+ * active pixels, and on return those that stay active; done >= 2. An active pixel is evaluated
+ * at n = done, a retired one (for nonfinite) at its n_p >= 2. e_out ([num_pixels], may be NULL)
+ * receives that e. stats (may be NULL): as izpi_gpu_progressive_adapt fills them, device_ms 0.
+ * Its error is izpi_host_last_error's. */
+int izpi_host_adapt(const double* sums, const double* moment2, const uint8_t* counted, const uint32_t* samples,
+                    uint8_t* active, uint32_t num_pixels, uint32_t done, uint32_t sampler, const izpi_noise_params* p,
+                    double* e_out, izpi_adapt_stats* stats);
+
 /* sizeof() of the boundary structs: 0 izpi_bvh4_node 1 izpi_texture 2 izpi_material
  * 3 izpi_camera 4 izpi_scene_desc 5 izpi_render_req 6 izpi_render_stats 7 izpi_hit
  * 8 izpi_tri_in 9 izpi_sphere_in 10 izpi_camera_in 11 izpi_scene_input 12 izpi_proto_info
  * 13 izpi_obj_info 14 izpi_obj_group 15 izpi_obj_material 16 izpi_render_tuning
- * 17 izpi_denoise_params 18 izpi_noise_params 19 izpi_noise_stats (0 = unknown). */
+ * 17 izpi_denoise_params 18 izpi_noise_params 19 izpi_noise_stats 20 izpi_adapt_stats
+ * (0 = unknown). */
 uint32_t izpi_abi_struct_size(int which);
 
 /* ======================================================================

@@ -29,6 +29,8 @@ OUT_CANVAS, OUT_PACKED = 0, 1
 POST_NONE, POST_SPECTRAL, POST_GAMMA_CLAMP = 0, 1, 2
 SNAP_CANVAS, SNAP_DISPLAY, SNAP_NOISE = 0, 1, 2  # izpi_gpu_progressive_snapshot's forms
 PROG_NOISE = 1  # izpi_gpu_progressive_begin_ex's flag: keep the samples' second moments
+PROG_ADAPTIVE = 4  # ... with PROG_NOISE: stop sampling the pixels an adapt() finds converged
+SNAP_SAMPLES = 3  # an adaptive session's sample-count map
 # placeholders from one look at a 40 x 40 Cornell box (include/izpi_gpu.h says why min_spp exists)
 NOISE_DEFAULT_THRESHOLD, NOISE_DEFAULT_FLOOR, NOISE_DEFAULT_TOLERATED, NOISE_DEFAULT_MIN_SPP = 0.25, 0.01, 0.05, 8
 FILTER_GAMMA, FILTER_CLAMP = 1, 2
@@ -175,6 +177,14 @@ class NoiseStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class AdaptStats(C.Structure):
+    _fields_ = [("pixels", C.c_uint64), ("nonfinite", C.c_uint64), ("active", C.c_uint64), ("retired", C.c_uint64),
+                ("samples", C.c_uint64), ("device_ms", C.c_double), ("done", C.c_uint32), ("converged", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class Hit(C.Structure):
     _fields_ = [("t", C.c_double), ("u", C.c_double), ("v", C.c_double), ("p", C.c_double * 3),
                 ("normal", C.c_double * 3), ("prim_ref", C.c_uint32), ("hit", C.c_uint32)]
@@ -239,7 +249,7 @@ class ObjMaterial(C.Structure):
 
 
 ABI_STRUCTS = [BVH4Node, Texture, Material, Camera, SceneDesc, RenderReq, RenderStats, Hit, TriIn, SphereIn, CameraIn,
-               SceneInput, ProtoInfo, ObjInfo, ObjGroup, ObjMaterial, RenderTuning, DenoiseParams, NoiseParams, NoiseStats]
+               SceneInput, ProtoInfo, ObjInfo, ObjGroup, ObjMaterial, RenderTuning, DenoiseParams, NoiseParams, NoiseStats, AdaptStats]
 
 # Symbols include/izpi_gpu.h and include/izpi_host.h declare (checked by tests).
 EXPORTS = [
@@ -267,6 +277,7 @@ EXPORTS = [
     "izpi_gpu_progressive_begin_ex", "izpi_gpu_progressive_noise", "izpi_gpu_progressive_converge",
     "izpi_gpu_multi_progressive_begin_ex", "izpi_gpu_multi_progressive_noise", "izpi_gpu_multi_progressive_converge",
     "izpi_host_noise",
+    "izpi_gpu_progressive_adapt", "izpi_gpu_multi_progressive_adapt", "izpi_host_adapt",
 ]
 
 _lib = None
@@ -328,6 +339,7 @@ def lib():
         getattr(L, pre + "end").argtypes = [C.c_void_p]
         getattr(L, pre + "begin_ex").argtypes = [C.c_void_p, C.POINTER(RenderReq), C.c_uint32, C.c_uint32]
         getattr(L, pre + "noise").argtypes = [C.c_void_p, C.POINTER(NoiseParams), C.POINTER(NoiseStats)]
+        getattr(L, pre + "adapt").argtypes = [C.c_void_p, C.POINTER(NoiseParams), C.POINTER(AdaptStats)]
         getattr(L, pre + "converge").argtypes = [C.c_void_p, C.POINTER(NoiseParams), C.POINTER(RenderStats),
                                                  C.POINTER(NoiseStats)]
     L.izpi_gpu_progressive_snapshot_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
@@ -384,6 +396,9 @@ def lib():
     # sums, moment2, counted, num_pixels, done, sampler, params, se_out, stats
     L.izpi_host_noise.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(NoiseParams), vp,
                                   C.POINTER(NoiseStats)]
+    # sums, moment2, counted, samples, active, num_pixels, done, sampler, params, e_out, stats
+    L.izpi_host_adapt.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(NoiseParams), vp,
+                                  C.POINTER(AdaptStats)]
     L.izpi_gpu_denoise_device.argtypes = [vp] + denoise_args + [c_double_p]
     L.izpi_scene_add_triangles.argtypes = [vp, vp, C.c_uint64, C.c_char_p]
     L.izpi_scene_background.argtypes = [vp, c_double_p, c_double_p, C.c_uint32]

@@ -614,6 +614,7 @@ uint32_t izpi_abi_struct_size(int which) {
     case 17: return sizeof(izpi_denoise_params);
     case 18: return sizeof(izpi_noise_params);
     case 19: return sizeof(izpi_noise_stats);
+    case 20: return sizeof(izpi_adapt_stats);
   }
   return 0;
 }

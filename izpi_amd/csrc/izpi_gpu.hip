@@ -103,13 +103,13 @@ struct CtxBuf {
   void** p;
   size_t* cap;
 };
-constexpr size_t RENDER_BUFS = 7, CTX_BUFS = 19;
+constexpr size_t RENDER_BUFS = 7, CTX_BUFS = 20;
 std::array<CtxBuf, CTX_BUFS> ctx_buffers(izpi_ctx* c) {
 #define IZPI_BUF(name) CtxBuf{(void**)&c->d_##name, &c->name##_cap}
   return {IZPI_BUF(samples), IZPI_BUF(recs), IZPI_BUF(pool), IZPI_BUF(ring), IZPI_BUF(running), IZPI_BUF(state),
           IZPI_BUF(spill), IZPI_BUF(out), IZPI_BUF(tiles), IZPI_BUF(utiles), IZPI_BUF(bg), IZPI_BUF(post),
           IZPI_BUF(share), IZPI_BUF(gather), IZPI_BUF(cpart), IZPI_BUF(finq), IZPI_BUF(denoise),
-          IZPI_BUF(moments), IZPI_BUF(noisepart)};
+          IZPI_BUF(moments), IZPI_BUF(noisepart), IZPI_BUF(adapt)};
 #undef IZPI_BUF
 }
 uint64_t buffer_bytes(izpi_ctx* ctx, size_t n) {
@@ -469,12 +469,20 @@ int render_body(izpi_ctx* ctx, const izpi_render_req* req, const RenderCall& cal
   if ((rc = begin_frame(ctx, req, rs, plan, call, nbg))) return rc;
   ShadeParams sp = shade_params(ctx, req, rs, plan);
   AccumParams ap = accum_params(ctx, req, rs, out_dev);
+  // An adaptive session's step over its active list: the list's entries are the step's tiles,
+  // one pixel each, and its pixels (entry j's samples lie where pixel j's would: the workspace
+  // planned for all pixels holds them).
+  const uint32_t run_pixels = call.list ? call.list_count : num_pixels;
+  if (call.list) {
+    sp.tile_w = sp.tile_h = 1; sp.tiles = call.list;
+    ap.num_pixels = run_pixels;
+  }
   if (!rs.preview) {
     path_shade_params(ctx, req, sc, rs, plan, nbg, sp);
     stage_tables(ctx, req, tu, rs, plan, nbg, sc, sp);
   }
 
-  const RunInput run{num_pixels, plan.chunk, plan.pool_blocks, sr};
+  const RunInput run{run_pixels, plan.chunk, plan.pool_blocks, sr, call.list, call.counts, call.samples_before};
   RunTimes times;
   float total_ms = 0;
   const double t_launch = host_ms();
@@ -521,7 +529,7 @@ int render_body(izpi_ctx* ctx, const izpi_render_req* req, const RenderCall& cal
   memset(&s, 0, sizeof(s));
   s.rays = cnt[CNT_RAYS]; s.node_visits = cnt[CNT_NODES]; s.tri_tests = cnt[CNT_TRI]; s.sph_tests = cnt[CNT_SPH];
   s.light_tri_tests = cnt[CNT_LTRI]; s.light_sph_tests = cnt[CNT_LSPH];
-  s.samples = (uint64_t)num_pixels * sr.end;
+  s.samples = call.list ? call.samples_before + (uint64_t)run_pixels * (sr.end - sr.begin) : (uint64_t)num_pixels * sr.end;
   s.kernel_ms = times.trace_ms; s.shade_ms = times.shade_ms; s.total_ms = total_ms; s.launches = times.launches; s.tail_ms = times.tail_ms;
   s.node_steps = cnt[CNT_NSTEP]; s.prim_steps = cnt[CNT_PSTEP]; s.leaf_shortcuts = cnt[CNT_SHORT];
   s.tail_node_visits = cnt[CNT_TAIL_NODES]; s.tail_tri_tests = cnt[CNT_TAIL_TRI]; s.tail_sph_tests = cnt[CNT_TAIL_SPH];

@@ -10,7 +10,7 @@
 //               [--progressive STEP [--snapshots PREFIX]]
 //               [--denoise [N] [--denoise-sigma c,n,a]]
 //               [--progressive STEP --noise-threshold T [--noise-tolerated F] [--noise-floor L]
-//                [--min-samples K] [--noise-out se.pfm]]
+//                [--min-samples K] [--noise-out se.pfm] [--adaptive [--samples-out n.pfm]]]
 //
 // --denoise [N] (--sampler colour or spectral) filters the frame with N iterations (default
 // IZPI_DENOISE_DEFAULT_ITERATIONS) of the edge-avoiding a-trous denoiser (izpi_gpu_denoise,
@@ -33,6 +33,14 @@
 // at the samples spent, byte for byte the file of a render at --samples done; --noise-out
 // gets the per-pixel standard errors (IZPI_SNAP_NOISE) as a PFM. --min-samples (default 8)
 // guards against the underestimated variance of the first few samples.
+//
+// --adaptive (with --progressive STEP --noise-threshold T; --sampler colour or spectral) stops
+// sampling the pixels whose own relative error is at most T (DESIGN.md section 3.10,
+// izpi_gpu_progressive_adapt): each evaluation prints one
+//   IZPI_ADAPT done= pixels= active= retired= nonfinite= samples=
+// line instead, and the render ends when at most --noise-tolerated of the finite pixels are
+// still active. Every pixel of --out is that pixel of a render at its own sample count;
+// --samples-out gets the counts (IZPI_SNAP_SAMPLES) as a PFM.
 //
 // Defaults are the Go shim's: the GPU-built tree and the forward accumulation
 // (IZPI_ACC_FORWARD; --accumulation recursive is bit-identical to the CPU oracle).
@@ -106,7 +114,8 @@ int main(int argc, char** argv) {
   bool noise = false;
   izpi_noise_params nparams = {IZPI_NOISE_DEFAULT_THRESHOLD, IZPI_NOISE_DEFAULT_FLOOR, IZPI_NOISE_DEFAULT_TOLERATED,
                                IZPI_NOISE_DEFAULT_MIN_SPP, 0};
-  std::string noise_out;
+  std::string noise_out, samples_out;
+  bool adaptive = false;
   double ink[3] = {0.0, 0.0, 0.0};
   bool quantized = false;
   uint32_t W = 1024, H = 1024, spp = 16, depth = 50, device = 0, gpus = 1;
@@ -147,6 +156,8 @@ int main(int argc, char** argv) {
     else if (a == "--noise-floor") nparams.floor = atof(val().c_str());
     else if (a == "--min-samples") nparams.min_spp = (uint32_t)atoi(val().c_str());
     else if (a == "--noise-out") noise_out = val();
+    else if (a == "--adaptive") adaptive = true;
+    else if (a == "--samples-out") samples_out = val();
     else if (a == "--ink") { if (sscanf(val().c_str(), "%lf,%lf,%lf", &ink[0], &ink[1], &ink[2]) != 3) die("--ink takes r,g,b"); }
     else die("unknown option " + a);
   }
@@ -156,6 +167,8 @@ int main(int argc, char** argv) {
   if (!snap_prefix.empty() && !progressive) die("--snapshots needs --progressive");
   if (noise && !progressive) die("--noise-threshold needs --progressive");
   if (!noise_out.empty() && !noise) die("--noise-out needs --noise-threshold");
+  if (adaptive && !noise) die("--adaptive needs --progressive and --noise-threshold");
+  if (!samples_out.empty() && !adaptive) die("--samples-out needs --adaptive");
   // ---- scene file (leader.go:54-75)
   std::vector<char> text;
   if (!read_file(scene_path, text)) die("cannot read " + scene_path);
@@ -202,6 +215,7 @@ int main(int argc, char** argv) {
   if (denoise && sampler != IZPI_SAMPLER_COLOUR && !spectral) die("--denoise needs --sampler colour or spectral");
   if (denoise && progressive) die("--denoise filters a whole frame: not with --progressive");
   if (denoise && png) die("--denoise filters linear values: not with --png-pipeline");
+  if (adaptive && sampler != IZPI_SAMPLER_COLOUR && !spectral) die("--adaptive needs --sampler colour or spectral");
   // ---- transport.ToScene, BVH, upload
   auto t0 = std::chrono::steady_clock::now();
   const izpi_scene_input* in = nullptr;
@@ -255,17 +269,26 @@ int main(int argc, char** argv) {
   std::vector<double> canvas((size_t)W * H * 4);
   std::vector<izpi_render_stats> stv(gpus > 1 ? gpus : 1);
   uint32_t spent = spp;  // samples per pixel in the canvas (fewer when the noise rule stopped the render)
+  uint64_t rendered = 0;  // --adaptive: the samples rendered, the sum of the pixels' own counts
   auto t1 = std::chrono::steady_clock::now();
   if (progressive) {
     // the frame in steps; a snapshot after each (the last one is the frame)
     auto ok = [&](int r) { if (r) die(multi ? izpi_gpu_multi_last_error(multi) : izpi_gpu_last_error(ctx)); };
-    const uint32_t flags = noise ? (uint32_t)IZPI_PROG_NOISE : 0u;
+    const uint32_t flags = (noise ? (uint32_t)IZPI_PROG_NOISE : 0u) | (adaptive ? (uint32_t)IZPI_PROG_ADAPTIVE : 0u);
     ok(multi ? izpi_gpu_multi_progressive_begin_ex(multi, &req, progressive, flags) : izpi_gpu_progressive_begin_ex(ctx, &req, progressive, flags));
     bool stop = false;
     for (uint32_t done = 0; done < spp && !stop;) {
       ok(multi ? izpi_gpu_multi_progressive_step(multi, 0, stv.data()) : izpi_gpu_progressive_step(ctx, 0, stv.data()));
       done = done + progressive < spp ? done + progressive : spp;
-      if (noise && done >= (nparams.min_spp > 2 ? nparams.min_spp : 2u)) {  // izpi_gpu_progressive_converge's rule, an evaluation at a time
+      if (adaptive && done >= (nparams.min_spp > 2 ? nparams.min_spp : 2u)) {  // ... and its rule on an adaptive session
+        izpi_adapt_stats as;
+        ok(multi ? izpi_gpu_multi_progressive_adapt(multi, &nparams, &as) : izpi_gpu_progressive_adapt(ctx, &nparams, &as));
+        fprintf(stderr, "IZPI_ADAPT done=%u pixels=%llu active=%llu retired=%llu nonfinite=%llu samples=%llu\n", as.done,
+                (unsigned long long)as.pixels, (unsigned long long)as.active, (unsigned long long)as.retired,
+                (unsigned long long)as.nonfinite, (unsigned long long)as.samples);
+        stop = as.converged != 0;
+        rendered = as.samples;
+      } else if (noise && done >= (nparams.min_spp > 2 ? nparams.min_spp : 2u)) {  // izpi_gpu_progressive_converge's rule, an evaluation at a time
         izpi_noise_stats ns;
         ok(multi ? izpi_gpu_multi_progressive_noise(multi, &nparams, &ns) : izpi_gpu_progressive_noise(ctx, &nparams, &ns));
         const uint64_t fin = ns.pixels - ns.nonfinite;
@@ -281,6 +304,12 @@ int main(int argc, char** argv) {
           ok(multi ? izpi_gpu_multi_progressive_snapshot(multi, IZPI_SNAP_NOISE, se.data())
                    : izpi_gpu_progressive_snapshot(ctx, IZPI_SNAP_NOISE, se.data()));
           write_pfm(noise_out, se, W, H);
+        }
+        if (!samples_out.empty()) {  // the sample-count map
+          std::vector<double> map((size_t)W * H * 4);
+          ok(multi ? izpi_gpu_multi_progressive_snapshot(multi, IZPI_SNAP_SAMPLES, map.data())
+                   : izpi_gpu_progressive_snapshot(ctx, IZPI_SNAP_SAMPLES, map.data()));
+          write_pfm(samples_out, map, W, H);
         }
       }
       if (snap_prefix.empty() && done < spp && !stop) continue;
@@ -321,7 +350,7 @@ int main(int argc, char** argv) {
   printf("{\"scene\": \"%s\", \"width\": %u, \"height\": %u, \"spp\": %u, \"bvh\": \"%s\", \"quantized\": %d, \"accumulation\": \"%s\", \"sampler\": \"%s\", \"gpus\": %u, "
          "\"setup_s\": %.3f, \"render_s\": %.4f, \"msamples_per_s\": %.2f, \"rays\": %llu, \"node_visits\": %llu}\n",
          scene_path.c_str(), W, H, spent, bvh.c_str(), bvh == "gpu" && quantized ? 1 : 0, acc.c_str(), sampler_name.c_str(), gpus > 1 ? gpus : 1u, setup_s, secs,
-         (double)W * H * spent / secs / 1e6, (unsigned long long)st.rays, (unsigned long long)st.node_visits);
+         (rendered ? (double)rendered : (double)W * H * spent) / secs / 1e6, (unsigned long long)st.rays, (unsigned long long)st.node_visits);
   // ---- outputs
   if (!out_raw.empty()) {
     FILE* f = fopen(out_raw.c_str(), "wb");

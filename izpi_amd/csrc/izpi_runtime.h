@@ -5,8 +5,8 @@
 //   session.hip     progressive sessions on one context, their noise estimate and stop rule;
 //   multi.hip       the share plan, device groups in one process (and their sessions), RCCL ranks;
 //   components.hip  post-processing and the component entries the tests call;
-//   trace.hip, wavefront.hip, preview.hip, resolve.hip, noise.hip, denoise.hip: the kernels a
-//                   render runs, each with its launch code.
+//   trace.hip, wavefront.hip, preview.hip, resolve.hip, noise.hip, adapt.hip, denoise.hip: the
+//                   kernels a render runs, each with its launch code.
 // The shade_*.hip units need none of this (izpi_kern.h). Not part of the ABI.
 #pragma once
 #include <atomic>
@@ -56,6 +56,7 @@ struct ResolveParams {
   const uint32_t* tiles;
   const double* running;  // [num_pixels][3]
   double* out;
+  const uint32_t* counts;  // an adaptive session after its first retirement: n_p per pixel, used for `done`; else null
 };
 void launch_resolve(hipStream_t st, const ResolveParams& rp);
 // k_noise_resolve and k_noise_stats (noise.hip): the noise estimate of a session begun with
@@ -70,9 +71,42 @@ struct NoiseParams {
   double* out;            // k_noise_resolve: (se_0, se_1, se_2, 1.0) per pixel, in k_resolve's layout
   double* block_sums;     // k_noise_stats: v[0] of each 256-pixel block, [ceil(num_pixels / 256)]
   unsigned long long* block_counts;  // k_noise_stats: each block's pixels, nonfinite, above and the bits of its largest e, [blocks][4]
+  const uint32_t* counts;  // an adaptive session after its first retirement: n_p per pixel, used for `done`; else null
 };
 void launch_noise_resolve(hipStream_t st, const NoiseParams& np);
 void launch_noise_stats(hipStream_t st, const NoiseParams& np);
+// k_adapt_select, k_adapt_scan and k_adapt_scatter (adapt.hip): izpi_gpu_progressive_adapt of a
+// session begun with IZPI_PROG_ADAPTIVE (noise.h). The sums and moments are
+// read only. All arrays are the context's d_adapt (AdaptBufs).
+struct AdaptParams {
+  uint32_t num_pixels, done, tile_w, tile_h, sampler, blocks;  // blocks = ceil(num_pixels / 256)
+  double threshold, floor;
+  const uint32_t* tiles;
+  const double* running;  // [num_pixels][3]
+  const double* moments;  // [num_pixels][3]
+  uint32_t* counts;       // [num_pixels]: n_p, the samples in pixel p's sums
+  uint8_t* state;         // [num_pixels]: 0 active, 1 retired, 2 retired as a counted non-finite pixel
+  uint32_t* table;        // [num_pixels][4]: the active list in packed order, (x, y, pixel, 0) per entry: the 1 x 1 tiles of a step
+  uint32_t* block_keep;   // [blocks]: k_adapt_select: each block's survivors; k_adapt_scan: the survivors before the block
+  uint32_t* block_stat;   // [blocks][2]: each block's counted and (counted) non-finite pixels
+  uint32_t* totals;       // [4]: active, counted, non-finite, 0
+};
+void launch_adapt(hipStream_t st, const AdaptParams& ap);
+// d_adapt of `pixels` pixels: the five arrays above at 16-B aligned offsets.
+struct AdaptBufs {
+  size_t counts, state, table, block_keep, block_stat, totals, bytes;
+  explicit AdaptBufs(size_t pixels) {
+    auto up = [](size_t v) { return (v + 15) / 16 * 16; };
+    const size_t blocks = (pixels + 255) / 256;
+    table = 0;
+    counts = table + pixels * 16;
+    block_keep = counts + up(pixels * 4);
+    block_stat = block_keep + up(blocks * 4);
+    totals = block_stat + up(blocks * 8);
+    state = totals + 16;
+    bytes = state + up(pixels);
+  }
+};
 // ================================================================ host side
 // The record sizes the workspace planner counts with (render_plan.h), against the real types.
 static_assert(sizeof(RayOD) == izpi_internal::plan_size::RAY && sizeof(PathHot) == izpi_internal::plan_size::PATH_HOT &&
@@ -144,6 +178,8 @@ struct izpi_ctx {
   // a session begun with IZPI_PROG_NOISE (noise.hip; both only grow, and no workspace plan counts them):
   double* d_moments = nullptr; size_t moments_cap = 0;  // the samples' second moments, [num_pixels][3]
   double* d_noisepart = nullptr; size_t noisepart_cap = 0;  // k_noise_stats' block partials: [blocks] sums, then [blocks][4] counts
+  // a session begun with IZPI_PROG_ADAPTIVE (adapt.hip; AdaptBufs; as above, it only grows and no plan counts it):
+  char* d_adapt = nullptr; size_t adapt_cap = 0;  // the per-pixel sample counts, the retirements, the active list
   uint32_t* h_count = nullptr;                        // pinned readback of d_misc (unit head, queue lengths; same stride) + scratch
   hipEvent_t ev3 = nullptr;
   hipEvent_t evb[3 * IZPI_PASS_BATCH] = {};
@@ -181,6 +217,12 @@ struct izpi_ctx {
     std::vector<double> bg_wl, bg_val;
     uint32_t step_spp = 0, done = 0;
     bool noise = false;  // IZPI_PROG_NOISE: the steps fold the second moments into d_moments
+    // IZPI_PROG_ADAPTIVE: `active` pixels still take samples, each with n_p == done;
+    // `listed` once a pixel has retired: the steps run over the active list and the snapshots
+    // read the per-pixel counts. samples = the sum of n_p over the session's pixels.
+    bool adaptive = false, listed = false;
+    uint32_t active = 0;
+    uint64_t samples = 0;
     // filled by render_body: the tiles rendered, their extent and pixels
     std::vector<uint32_t> run_tiles;
     uint32_t tile_w = 0, tile_h = 0, num_pixels = 0;
@@ -239,7 +281,13 @@ int trace_ring(const Tracer& t);  // entries of the instance's LDS stack ring (d
 // What a run of the chunk loops (run_wavefront, run_preview) is given: the pixels of the request's
 // tiles, the samples per pixel and chunk, the overflow record blocks (the path samplers), the
 // sample range; and what it reports: the device times of its passes and their number.
-struct RunInput { uint32_t num_pixels, chunk, pool_blocks; SampleRange range; };
+// An adaptive session's step over its active list (SampleRange::keep): num_pixels entries of
+// `list` (AdaptParams::table), k_accumulate's scatter instance with `counts`; its progress
+// starts at samples_before samples. A null list: every other run.
+struct RunInput {
+  uint32_t num_pixels, chunk, pool_blocks; SampleRange range;
+  const uint32_t* list = nullptr; uint32_t* counts = nullptr; uint64_t samples_before = 0;
+};
 struct RunTimes { float trace_ms = 0, shade_ms = 0, tail_ms = 0; uint32_t launches = 0; };
 // wavefront.hip: the shading instance a scene runs, the smallest that holds its material kinds
 // (matset: its MS_* bits; const_basic: Lambertian + DiffuseLight with constant albedos, whose
@@ -252,6 +300,9 @@ int run_wavefront(izpi_ctx* ctx, const izpi_render_req* req, const DevScene& sc,
 int prepare_wavefront(izpi_ctx* ctx, const ShadeKernels& k);
 int prepare_accumulate(izpi_ctx* ctx);
 void launch_accumulate(hipStream_t st, const AccumParams& ap, double* moments = nullptr);
+// ... and of its scatter instance: entry j of `list` adds its samples to pixel list[4 * j + 2]'s
+// sums and moments and ap.chunk_spp to its count (ap.num_pixels entries; never the last chunk).
+void launch_accumulate_list(hipStream_t st, const AccumParams& ap, double* moments, const uint32_t* list, uint32_t* counts);
 // The moments k_accumulate folds besides the sums: those of a noise session's steps, else none
 // (the present instance runs).
 inline double* session_moments(const izpi_ctx* ctx, const SampleRange& r) {
@@ -297,10 +348,17 @@ int upload_packed(izpi_ctx* ctx, const izpi_scene_desc* d, const PackedScene& ps
 // How a render call is driven: the samples it renders, the samples its workspace is sized
 // for (the request's, or a progressive session's step_spp: the sums then stay in d_running),
 // and whether it stops once the workspace is allocated (izpi_gpu_prepare, a session's begin).
+// list: an adaptive session's step over the `list_count` entries of its device-built active
+// list instead of the request's tiles (AdaptParams::table; counts: the pixels' sample counts;
+// samples_before: what the session has rendered). The workspace is the one planned for all pixels.
 struct RenderCall {
   SampleRange range;
   uint32_t size_spp;
   bool prepare_only;
+  const uint32_t* list = nullptr;
+  uint32_t* counts = nullptr;
+  uint32_t list_count = 0;
+  uint64_t samples_before = 0;
 };
 inline RenderCall one_shot(const izpi_render_req* req, bool prepare_only = false) {
   const uint32_t spp = req ? req->spp : 0;
@@ -329,11 +387,33 @@ void session_drop(izpi_ctx* ctx);
 int session_begin(izpi_ctx* ctx, const izpi_render_req* req, uint32_t step_spp, uint32_t flags);
 int session_step(izpi_ctx* ctx, uint32_t spp, izpi_render_stats* stats);
 int session_noise(izpi_ctx* ctx, const izpi_noise_params* params, izpi_noise_stats* out);
+int session_adapt(izpi_ctx* ctx, const izpi_noise_params* params, izpi_adapt_stats* out);
 int session_snapshot(izpi_ctx* ctx, uint32_t form, double* out_dev);
 // The checks a context's session and a group's share (each true / false with the message in err).
 bool session_lacks_noise(const izpi_ctx::Session& ss, std::string& err, uint32_t need = 2);
 bool noise_params_ok(const izpi_noise_params* params, izpi_noise_params& p, std::string& err);
 bool snapshot_form_ok(uint32_t form, uint32_t done, std::string& err);
+bool session_lacks_adaptive(const izpi_ctx::Session& ss, std::string& err);
+// converge on an adaptive session: step(step_spp), then adapt once done >= max(2, min_spp), until
+// the frame rule holds or the cap is reached. A step that leaves done where it was found no
+// active pixel (an earlier adapt retired them all, at any done >= 2): nothing is left to render,
+// and the loop ends there (*idle), whatever min_spp is.
+template <class Step, class Adapt, class Done>
+int adapt_loop(const izpi_noise_params& p, uint32_t cap, Step step, Adapt adapt, Done done, izpi_adapt_stats* out, bool* idle) {
+  izpi_adapt_stats last{};
+  int rc = IZPI_OK;
+  *idle = false;
+  while (!rc && done() < cap) {
+    const uint32_t before = done();
+    if ((rc = step())) break;
+    if (done() == before) { *idle = true; break; }
+    if (done() < std::max(2u, p.min_spp)) continue;
+    if ((rc = adapt(p, &last))) break;
+    if (last.converged) break;
+  }
+  if (out) *out = last;
+  return rc;
+}
 // converge: step(step_spp), then the statistic once done >= max(2, min_spp), until the frame is
 // converged or the cap is reached. `step` and `noise` are the session's own (one context or
 // the devices of a group); done() reads its samples; p is checked (noise_params_ok).

@@ -355,7 +355,9 @@ int izpi_gpu_multi_progressive_begin_ex(izpi_multi* m, const izpi_render_req* re
   if (!multi_valid(m)) return IZPI_ERR_INVALID;
   if (m->prog_open) { m->err = "a progressive session is already open"; return IZPI_ERR_INVALID; }
   if (!req || step_spp == 0) { m->err = "progressive_begin: a request and step_spp >= 1"; return IZPI_ERR_INVALID; }
-  if (flags & ~(uint32_t)IZPI_PROG_NOISE) { m->err = "progressive_begin: unknown flags"; return IZPI_ERR_INVALID; }
+  if (flags & ~(uint32_t)(IZPI_PROG_NOISE | IZPI_PROG_ADAPTIVE)) { m->err = "progressive_begin: unknown flags"; return IZPI_ERR_INVALID; }
+  if ((flags & IZPI_PROG_ADAPTIVE) && !(flags & IZPI_PROG_NOISE)) { m->err = "progressive_begin: IZPI_PROG_ADAPTIVE needs IZPI_PROG_NOISE"; return IZPI_ERR_INVALID; }
+  if ((flags & IZPI_PROG_ADAPTIVE) && preview_sampler(req->sampler)) { m->err = "progressive_begin: IZPI_PROG_ADAPTIVE with a preview sampler"; return IZPI_ERR_INVALID; }
   for (izpi_ctx* c : m->ctx)
     if (c->session.open) { m->err = "a context of this group has a progressive session of its own"; return IZPI_ERR_INVALID; }
   int rc = session_copy_request(m->session, req, m->err);
@@ -382,6 +384,7 @@ int izpi_gpu_multi_progressive_begin_ex(izpi_multi* m, const izpi_render_req* re
     return rc;
   }
   ms.noise = (flags & IZPI_PROG_NOISE) != 0;
+  ms.adaptive = (flags & IZPI_PROG_ADAPTIVE) != 0;  // (ms.listed: an adapt has run, and ms.active is the devices' sum)
   m->shares = sh;
   m->prog_open = true;
   return IZPI_OK;
@@ -390,7 +393,11 @@ int izpi_gpu_multi_progressive_begin_ex(izpi_multi* m, const izpi_render_req* re
 int izpi_gpu_multi_progressive_step(izpi_multi* m, uint32_t spp, izpi_render_stats* stats) {
   if (!multi_in_session(m)) return IZPI_ERR_INVALID;
   izpi_ctx::Session& ms = m->session;
-  const uint32_t n = std::min(spp ? spp : ms.step_spp, ms.req.spp - ms.done);
+  uint32_t n = std::min(spp ? spp : ms.step_spp, ms.req.spp - ms.done);
+  if (ms.listed && ms.active == 0) n = 0;  // an adaptive session with no active pixel on any device
+  // (A device whose own share has retired renders nothing and keeps its session's done where it
+  // was: a device session's done may lag ms.done. Nothing reads it there: its snapshots and
+  // statistic use the per-pixel counts, and its adapt finds no active pixel to evaluate.)
   int rc = IZPI_OK;
   if (n) rc = on_every_device(m, [&](uint32_t, izpi_ctx* c) { return c->session.open ? session_step(c, n, nullptr) : (int)IZPI_OK; });
   for (size_t i = 0; stats && i < m->ctx.size(); i++) stats[i] = m->ctx[i]->session.cum;
@@ -404,6 +411,7 @@ int izpi_gpu_multi_progressive_snapshot(izpi_multi* m, uint32_t form, double* ou
   const izpi_ctx::Session& ms = m->session;
   if (!snapshot_form_ok(form, ms.done, m->err)) return IZPI_ERR_INVALID;
   if (form == IZPI_SNAP_NOISE && session_lacks_noise(ms, m->err)) return IZPI_ERR_INVALID;
+  if (form == IZPI_SNAP_SAMPLES && session_lacks_adaptive(ms, m->err)) return IZPI_ERR_INVALID;
   izpi_render_req q = ms.req;
   if (form != IZPI_SNAP_CANVAS) q.post = IZPI_POST_NONE;  // the display pixels and the standard errors are not post-processed
   // every device with a share resolves its sums into its packed block
@@ -434,10 +442,44 @@ int izpi_gpu_multi_progressive_noise(izpi_multi* m, const izpi_noise_params* p, 
   return IZPI_OK;
 }
 
+// Every device adapts its own share (the rule is per pixel); the integers are added, the
+// slowest device's time is the call's, and the frame rule reads the sums.
+int izpi_gpu_multi_progressive_adapt(izpi_multi* m, const izpi_noise_params* p, izpi_adapt_stats* out) {
+  if (!multi_in_session(m)) return IZPI_ERR_INVALID;
+  izpi_noise_params q;
+  izpi_ctx::Session& ms = m->session;
+  if (!noise_params_ok(p, q, m->err) || session_lacks_adaptive(ms, m->err)) return IZPI_ERR_INVALID;
+  if (ms.done < 2) { m->err = "adapt: needs at least 2 samples"; return IZPI_ERR_INVALID; }
+  std::vector<izpi_adapt_stats> part(m->ctx.size());
+  const int rc = on_every_device(m, [&](uint32_t i, izpi_ctx* c) { return c->session.open ? session_adapt(c, &q, &part[i]) : (int)IZPI_OK; });
+  if (rc) return rc;
+  izpi_adapt_stats s{};
+  for (const izpi_adapt_stats& d : part) {
+    s.pixels += d.pixels; s.nonfinite += d.nonfinite; s.active += d.active; s.retired += d.retired; s.samples += d.samples;
+    s.device_ms = std::max(s.device_ms, d.device_ms);
+  }
+  ms.listed = true; ms.active = (uint32_t)s.active;
+  s.done = ms.done;
+  s.converged = nz::converged(s.pixels, s.nonfinite, s.active, s.done, q);
+  if (out) *out = s;
+  return IZPI_OK;
+}
+
 int izpi_gpu_multi_progressive_converge(izpi_multi* m, const izpi_noise_params* p, izpi_render_stats* stats, izpi_noise_stats* noise) {
   if (!multi_in_session(m)) return IZPI_ERR_INVALID;
   izpi_noise_params q;
   if (!noise_params_ok(p, q, m->err) || session_lacks_noise(m->session, m->err, 0)) return IZPI_ERR_INVALID;
+  if (m->session.adaptive) {
+    izpi_adapt_stats last{};
+    bool idle = false;
+    int rc = adapt_loop(q, m->session.req.spp, [&]() { return izpi_gpu_multi_progressive_step(m, 0, stats); },
+                        [&](const izpi_noise_params& np, izpi_adapt_stats* as) { return izpi_gpu_multi_progressive_adapt(m, &np, as); },
+                        [&]() { return m->session.done; }, &last, &idle);
+    izpi_noise_stats ns{};
+    if (!rc && (last.done || idle)) rc = izpi_gpu_multi_progressive_noise(m, &q, &ns);
+    if (noise) *noise = ns;
+    return rc;
+  }
   return converge_loop(q, m->session.req.spp, [&]() { return izpi_gpu_multi_progressive_step(m, 0, stats); },
                        [&](const izpi_noise_params& np, izpi_noise_stats* ns) { return izpi_gpu_multi_progressive_noise(m, &np, ns); },
                        [&]() { return m->session.done; }, noise);

@@ -66,6 +66,12 @@ IZPI_HD bool pixel(const double s[3], const double m2[3], uint32_t n, bool spect
   return finite(s[0]) && finite(s[1]) && finite(s[2]) && finite(m2[0]) && finite(m2[1]) && finite(m2[2]) && finite(*e);
 }
 
+// Adaptive sampling (deviation A26): evaluated at n = done, an active
+// pixel goes on taking samples iff it is counted (sample row y >= 1), finite and its e is above
+// the threshold. Every other pixel retires for good with the samples it has: the uncounted
+// never reach a canvas, and a non-finite pixel can never converge.
+IZPI_HD bool stays_active(bool counted, bool fin, double e, double threshold) { return counted && fin && e > threshold; }
+
 // The stop rule over the frame's integers (order-free, so every share plan decides alike).
 inline uint32_t converged(uint64_t pixels, uint64_t nonfinite, uint64_t above, uint32_t done, const izpi_noise_params& p) {
   return done >= p.min_spp && (double)above <= p.tolerated * (double)(pixels - nonfinite) ? 1u : 0u;

@@ -25,6 +25,10 @@ __device__ __forceinline__ void pixel_xy(const NoiseParams& np, uint32_t p, uint
   *y = np.tiles[4 * tile + 1] + in_tile / np.tile_w;
 }
 
+// The samples in pixel p's sums: an adaptive session's own count once a pixel has retired
+// (DESIGN.md section 3.10), else the session's.
+__device__ __forceinline__ uint32_t pixel_n(const NoiseParams& np, uint32_t p) { return np.counts ? np.counts[p] : np.done; }
+
 }  // namespace
 
 // One thread per pixel in packed order: 48 B of sums and moments in, 32 B out; HBM-streaming.
@@ -34,7 +38,7 @@ __global__ void __launch_bounds__(256) k_noise_resolve(const NoiseParams np) {
   if (p >= np.num_pixels) return;
   double s[3], m2[3], se[3], e;
   load_pixel(np, p, s, m2);
-  nz::pixel(s, m2, np.done, np.sampler == IZPI_SAMPLER_SPECTRAL, np.floor, se, &e);
+  nz::pixel(s, m2, pixel_n(np, p), np.sampler == IZPI_SAMPLER_SPECTRAL, np.floor, se, &e);
   double* o;
   if (np.out_layout == IZPI_OUT_PACKED) {
     o = np.out + (size_t)p * 4;
@@ -70,7 +74,7 @@ __global__ void __launch_bounds__(nz::BLOCK) k_noise_stats(const NoiseParams np)
     counted = y >= 1;
     double s[3], m2[3], se[3];
     load_pixel(np, p, s, m2);
-    fin = nz::pixel(s, m2, np.done, np.sampler == IZPI_SAMPLER_SPECTRAL, np.floor, se, &e);
+    fin = nz::pixel(s, m2, pixel_n(np, p), np.sampler == IZPI_SAMPLER_SPECTRAL, np.floor, se, &e);
   }
   const bool good = counted && fin;
   const double mine = good ? e : 0.0;

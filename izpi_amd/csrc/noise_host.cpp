@@ -56,3 +56,45 @@ extern "C" int izpi_host_noise(const double* sums, const double* moment2, const 
   if (out) *out = st;
   return IZPI_OK;
 }
+
+// izpi_host_adapt: one evaluation of the adaptive rule, the twin of
+// k_adapt_select (adapt.hip) and of the integers the host adds up after it.
+extern "C" int izpi_host_adapt(const double* sums, const double* moment2, const uint8_t* counted, const uint32_t* samples,
+                               uint8_t* active, uint32_t num_pixels, uint32_t done, uint32_t sampler,
+                               const izpi_noise_params* params, double* e_out, izpi_adapt_stats* out) {
+  const izpi_noise_params p = params ? *params : nz::defaults();
+  const char* bad = nz::check_params(p);
+  if (!bad && (!sums || !moment2)) bad = "adapt: sums and moment2 must be given";
+  if (!bad && (!samples || !active)) bad = "adapt: samples and active must be given";
+  if (!bad && done < 2) bad = "adapt: needs at least 2 samples";
+  if (!bad && (sampler != IZPI_SAMPLER_COLOUR && sampler != IZPI_SAMPLER_SPECTRAL)) bad = "adapt: the Colour or the Spectral sampler";
+  if (bad) {
+    izpi_internal::set_host_error(bad);
+    return IZPI_ERR_INVALID;
+  }
+  const bool spectral = sampler == IZPI_SAMPLER_SPECTRAL;
+  izpi_adapt_stats st{};
+  st.done = done;
+  for (uint64_t px = 0; px < num_pixels; px++) {
+    const bool is_counted = !counted || counted[px];
+    const uint32_t n = active[px] ? done : samples[px];
+    double se[3], e = 0.0;
+    const bool fin = n >= 2 ? nz::pixel(sums + 3 * px, moment2 + 3 * px, n, spectral, p.floor, se, &e) : true;
+    if (e_out) e_out[px] = e;
+    if (is_counted) {
+      st.pixels++;
+      if (!fin) st.nonfinite++;
+    }
+    st.samples += n;
+    if (!active[px]) continue;
+    if (nz::stays_active(is_counted, fin, e, p.threshold)) {
+      st.active++;
+    } else {
+      active[px] = 0;
+      st.retired++;
+    }
+  }
+  st.converged = nz::converged(st.pixels, st.nonfinite, st.active, done, p);
+  if (out) *out = st;
+  return IZPI_OK;
+}

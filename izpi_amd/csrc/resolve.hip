@@ -13,15 +13,20 @@
 //  IZPI_SNAP_DISPLAY: the pixel display.DisplayTile shows (rgb.go:43-51, spectral.go:38-46):
 //    B, G, R, 1.0; for Spectral XYZToACEScg of (X, Y, Z) * exposure (rgb_image.go:13-22), each
 //    row (m0 * x + m1 * y) + m2 * z in that order.
+//  IZPI_SNAP_SAMPLES (an adaptive session): (n, n, n, 1.0), n the pixel's sample count.
 __global__ void __launch_bounds__(256) k_resolve(const ResolveParams rp) {
   const uint32_t p = blockIdx.x * 256 + threadIdx.x;
   if (p >= rp.num_pixels) return;
   const double c0 = rp.running[3 * (size_t)p], c1 = rp.running[3 * (size_t)p + 1], c2 = rp.running[3 * (size_t)p + 2];
+  // (an adaptive session after its first retirement: the pixel's own sample count)
+  const uint32_t n = rp.counts ? rp.counts[p] : rp.done;
   double r0, r1, r2;
-  if (rp.sampler != IZPI_SAMPLER_SPECTRAL) {  // vec3.ScalarDiv(col, numSamples)
-    r0 = c0 / (double)rp.done; r1 = c1 / (double)rp.done; r2 = c2 / (double)rp.done;
+  if (rp.form == IZPI_SNAP_SAMPLES) {  // the sample-count map
+    r0 = r1 = r2 = (double)n;
+  } else if (rp.sampler != IZPI_SAMPLER_SPECTRAL) {  // vec3.ScalarDiv(col, numSamples)
+    r0 = c0 / (double)n; r1 = c1 / (double)n; r2 = c2 / (double)n;
   } else {  // sum * (1/numSamples)
-    const double inv = 1.0 / (double)rp.done;
+    const double inv = 1.0 / (double)n;
     r0 = c0 * inv; r1 = c1 * inv; r2 = c2 * inv;
   }
   if (rp.form == IZPI_SNAP_DISPLAY) {

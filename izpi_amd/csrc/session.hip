@@ -1,6 +1,7 @@
 // session.hip — progressive sessions on one context (izpi_gpu_progressive_*): the samples of a
 // request in resumable steps, snapshots of the running sums, the noise estimate and its stop
-// rule (noise.h). A device group's session (multi.hip) is one of these per device.
+// rule, adaptive sampling by that estimate (noise.h). A device group's session (multi.hip) is
+// one of these per device.
 #include "izpi_runtime.h"
 #include "noise.h"
 
@@ -43,6 +44,34 @@ static int session_zero_moments(izpi_ctx* ctx) {
   return IZPI_OK;
 }
 
+// The arrays of d_adapt (AdaptBufs) for the session's pixels.
+static AdaptParams adapt_arrays(izpi_ctx* ctx) {
+  const izpi_ctx::Session& ss = ctx->session;
+  const AdaptBufs ab(ss.num_pixels);
+  AdaptParams a{};
+  a.num_pixels = ss.num_pixels; a.blocks = (ss.num_pixels + 255) / 256;
+  a.table = (uint32_t*)(ctx->d_adapt + ab.table); a.counts = (uint32_t*)(ctx->d_adapt + ab.counts);
+  a.block_keep = (uint32_t*)(ctx->d_adapt + ab.block_keep); a.block_stat = (uint32_t*)(ctx->d_adapt + ab.block_stat);
+  a.totals = (uint32_t*)(ctx->d_adapt + ab.totals); a.state = (uint8_t*)(ctx->d_adapt + ab.state);
+  return a;
+}
+// The per-pixel counts the snapshots and the statistic read: an adaptive session's once a pixel
+// has retired; until then every pixel has `done` samples, and the plain forms run.
+static const uint32_t* session_counts(izpi_ctx* ctx) {
+  return ctx->session.listed ? adapt_arrays(ctx).counts : nullptr;
+}
+// IZPI_PROG_ADAPTIVE: every pixel active with no sample, in a buffer of its own.
+static int session_zero_adapt(izpi_ctx* ctx) {
+  izpi_ctx::Session& ss = ctx->session;
+  const AdaptBufs ab(ss.num_pixels);
+  const int rc = grow(ctx, (void**)&ctx->d_adapt, &ctx->adapt_cap, ab.bytes);
+  if (rc) return rc;
+  HIP_TRY(hipMemsetAsync(ctx->d_adapt, 0, ab.bytes, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  ss.adaptive = true; ss.listed = false; ss.active = ss.num_pixels; ss.samples = 0;
+  return IZPI_OK;
+}
+
 // begin: render_body's own checks, plan and allocation for a request of step_spp samples
 // (its prepare_only form, which for a session also zeroes the sums and the counters).
 // With IZPI_PROG_NOISE the samples' second moments start at zero in a buffer of their own
@@ -50,7 +79,9 @@ static int session_zero_moments(izpi_ctx* ctx) {
 int session_begin(izpi_ctx* ctx, const izpi_render_req* req, uint32_t step_spp, uint32_t flags) {
   if (ctx->session.open) { ctx->err = "a progressive session is already open"; return IZPI_ERR_INVALID; }
   if (!req || step_spp == 0) { ctx->err = "progressive_begin: a request and step_spp >= 1"; return IZPI_ERR_INVALID; }
-  if (flags & ~(uint32_t)IZPI_PROG_NOISE) { ctx->err = "progressive_begin: unknown flags"; return IZPI_ERR_INVALID; }
+  if (flags & ~(uint32_t)(IZPI_PROG_NOISE | IZPI_PROG_ADAPTIVE)) { ctx->err = "progressive_begin: unknown flags"; return IZPI_ERR_INVALID; }
+  if ((flags & IZPI_PROG_ADAPTIVE) && !(flags & IZPI_PROG_NOISE)) { ctx->err = "progressive_begin: IZPI_PROG_ADAPTIVE needs IZPI_PROG_NOISE"; return IZPI_ERR_INVALID; }
+  if ((flags & IZPI_PROG_ADAPTIVE) && preview_sampler(req->sampler)) { ctx->err = "progressive_begin: IZPI_PROG_ADAPTIVE with a preview sampler"; return IZPI_ERR_INVALID; }
   izpi_ctx::Session& ss = ctx->session;
   int rc = session_copy_request(ss, req, ctx->err);
   if (!rc) {
@@ -58,6 +89,7 @@ int session_begin(izpi_ctx* ctx, const izpi_render_req* req, uint32_t step_spp, 
     rc = render_body(ctx, &ss.req, RenderCall{SampleRange{0, 0, true}, ss.step_spp, true}, nullptr);
   }
   if (!rc && (flags & IZPI_PROG_NOISE)) rc = session_zero_moments(ctx);
+  if (!rc && (flags & IZPI_PROG_ADAPTIVE)) rc = session_zero_adapt(ctx);
   if (rc) {
     const std::string why = ctx->err;
     session_drop(ctx);
@@ -78,25 +110,34 @@ static int session_usable(izpi_ctx* ctx) {
 }
 
 // step: samples [done, done + n) through render_body's chunk loops, never finalised. The
-// device counters run on from step to step; times and launches are summed here.
+// device counters run on from step to step; times and launches are summed here. An adaptive
+// session after its first retirement: the same over its active list (render_body), and with no
+// active pixel nothing.
 int session_step(izpi_ctx* ctx, uint32_t spp, izpi_render_stats* stats) {
   int rc = session_usable(ctx);
   if (rc) return rc;
   izpi_ctx::Session& ss = ctx->session;
-  const uint32_t n = std::min(spp ? spp : ss.step_spp, ss.req.spp - ss.done);
+  uint32_t n = std::min(spp ? spp : ss.step_spp, ss.req.spp - ss.done);
+  if (ss.listed && ss.active == 0) n = 0;
   if (n) {
-    rc = render_body(ctx, &ss.req, RenderCall{SampleRange{ss.done, ss.done + n, true}, ss.step_spp, false}, nullptr);
+    RenderCall call{SampleRange{ss.done, ss.done + n, true}, ss.step_spp, false};
+    if (ss.listed) {
+      const AdaptParams a = adapt_arrays(ctx);
+      call.list = a.table; call.counts = a.counts; call.list_count = ss.active; call.samples_before = ss.samples;
+    }
+    rc = render_body(ctx, &ss.req, call, nullptr);
     if (rc) {  // a chunk may or may not be in the sums
       ss.broken = true;
       return rc;
     }
     ss.done += n;
+    ss.samples += (uint64_t)n * (ss.adaptive ? ss.active : ss.num_pixels);
     izpi_render_stats s = ctx->last;
     s.kernel_ms += ss.cum.kernel_ms; s.shade_ms += ss.cum.shade_ms; s.tail_ms += ss.cum.tail_ms;
     s.total_ms += ss.cum.total_ms; s.alloc_ms += ss.cum.alloc_ms; s.launches += ss.cum.launches;
     ss.cum = s;
     ctx->last = s;
-    ctx->prog_done.store((uint64_t)ss.num_pixels * ss.done, std::memory_order_relaxed);
+    ctx->prog_done.store(ss.samples, std::memory_order_relaxed);
   }
   if (stats) *stats = ss.cum;
   return IZPI_OK;
@@ -127,9 +168,14 @@ bool noise_params_ok(const izpi_noise_params* params, izpi_noise_params& p, std:
 }
 // A snapshot's form is known, and the session has a sample to show.
 bool snapshot_form_ok(uint32_t form, uint32_t done, std::string& err) {
-  if (form != IZPI_SNAP_CANVAS && form != IZPI_SNAP_DISPLAY && form != IZPI_SNAP_NOISE) { err = "unknown snapshot form"; return false; }
+  if (form != IZPI_SNAP_CANVAS && form != IZPI_SNAP_DISPLAY && form != IZPI_SNAP_NOISE && form != IZPI_SNAP_SAMPLES) { err = "unknown snapshot form"; return false; }
   if (done == 0) { err = "snapshot before the session's first sample"; return false; }
   return true;
+}
+// adapt, and the IZPI_SNAP_SAMPLES snapshot, need a session begun with IZPI_PROG_ADAPTIVE.
+bool session_lacks_adaptive(const izpi_ctx::Session& ss, std::string& err) {
+  if (!ss.adaptive) err = "adapt: the session was begun without IZPI_PROG_ADAPTIVE";
+  return !ss.adaptive;
 }
 static NoiseParams noise_params(izpi_ctx* ctx) {
   const izpi_ctx::Session& ss = ctx->session;
@@ -138,6 +184,7 @@ static NoiseParams noise_params(izpi_ctx* ctx) {
   np.tile_w = ss.tile_w; np.tile_h = ss.tile_h; np.sampler = ss.req.sampler; np.out_layout = ss.req.out_layout;
   np.threshold = IZPI_NOISE_DEFAULT_THRESHOLD; np.floor = IZPI_NOISE_DEFAULT_FLOOR;
   np.tiles = ctx->d_tiles; np.running = ctx->d_running; np.moments = ctx->d_moments;
+  np.counts = session_counts(ctx);
   return np;
 }
 
@@ -182,6 +229,41 @@ int session_noise(izpi_ctx* ctx, const izpi_noise_params* params, izpi_noise_sta
   return IZPI_OK;
 }
 
+// adapt: adapt.hip's three launches over the session's pixels; the frame's integers come back
+// in one small copy. From the first retirement on the steps run over the list it leaves.
+int session_adapt(izpi_ctx* ctx, const izpi_noise_params* params, izpi_adapt_stats* out) {
+  int rc = session_usable(ctx);
+  if (rc) return rc;
+  izpi_noise_params p;
+  izpi_ctx::Session& ss = ctx->session;
+  if (!noise_params_ok(params, p, ctx->err) || session_lacks_adaptive(ss, ctx->err)) return IZPI_ERR_INVALID;
+  if (ss.done < 2) { ctx->err = "adapt: needs at least 2 samples"; return IZPI_ERR_INVALID; }
+  hipStream_t st = ctx->stream;
+  if ((rc = session_tiles(ctx))) return rc;
+  AdaptParams a = adapt_arrays(ctx);
+  a.done = ss.done; a.tile_w = ss.tile_w; a.tile_h = ss.tile_h; a.sampler = ss.req.sampler;
+  a.threshold = p.threshold; a.floor = p.floor;
+  a.tiles = ctx->d_tiles; a.running = ctx->d_running; a.moments = ctx->d_moments;
+  HIP_TRY(hipEventRecord(ctx->ev0, st));
+  launch_adapt(st, a);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(ctx->ev1, st));
+  uint32_t totals[4] = {0, 0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(totals, a.totals, sizeof(totals), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  float ms = 0;
+  HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+  if (totals[0] > ss.active) { ctx->err = "adapt: the active list grew"; ss.broken = true; return IZPI_ERR_DEVICE; }
+  izpi_adapt_stats s{};
+  s.pixels = totals[1]; s.nonfinite = totals[2]; s.active = totals[0]; s.retired = ss.active - totals[0];
+  ss.active = totals[0];
+  if (ss.active < ss.num_pixels) ss.listed = true;
+  s.samples = ss.samples; s.device_ms = ms; s.done = ss.done;
+  s.converged = nz::converged(s.pixels, s.nonfinite, s.active, s.done, p);
+  if (out) *out = s;
+  return IZPI_OK;
+}
+
 // snapshot: k_resolve of the sums into device memory, then (IZPI_SNAP_CANVAS) the request's post.
 int session_snapshot(izpi_ctx* ctx, uint32_t form, double* out_dev) {
   int rc = session_usable(ctx);
@@ -189,6 +271,7 @@ int session_snapshot(izpi_ctx* ctx, uint32_t form, double* out_dev) {
   const izpi_ctx::Session& ss = ctx->session;
   if (!snapshot_form_ok(form, ss.done, ctx->err)) return IZPI_ERR_INVALID;
   if (form == IZPI_SNAP_NOISE && session_lacks_noise(ss, ctx->err)) return IZPI_ERR_INVALID;
+  if (form == IZPI_SNAP_SAMPLES && session_lacks_adaptive(ss, ctx->err)) return IZPI_ERR_INVALID;
   if (!out_dev) { ctx->err = "null output"; return IZPI_ERR_INVALID; }
   hipStream_t st = ctx->stream;
   if ((rc = session_tiles(ctx))) return rc;
@@ -205,6 +288,7 @@ int session_snapshot(izpi_ctx* ctx, uint32_t form, double* out_dev) {
   rp.tile_w = ss.tile_w; rp.tile_h = ss.tile_h; rp.sampler = ss.req.sampler; rp.out_layout = ss.req.out_layout;
   rp.form = form; rp.exposure = ss.req.exposure;
   rp.tiles = ctx->d_tiles; rp.running = ctx->d_running; rp.out = out_dev;
+  rp.counts = session_counts(ctx);
   launch_resolve(st, rp);
   HIP_TRY(hipGetLastError());
   if (form == IZPI_SNAP_CANVAS && (rc = apply_post(ctx, &ss.req, out_dev))) return rc;
@@ -234,6 +318,12 @@ int izpi_gpu_progressive_noise(izpi_ctx* ctx, const izpi_noise_params* p, izpi_n
   return session_noise(ctx, p, out);
 }
 
+int izpi_gpu_progressive_adapt(izpi_ctx* ctx, const izpi_noise_params* p, izpi_adapt_stats* out) {
+  if (!ctx) return IZPI_ERR_INVALID;
+  HIP_TRY(hipSetDevice(ctx->device));
+  return session_adapt(ctx, p, out);
+}
+
 int izpi_gpu_progressive_converge(izpi_ctx* ctx, const izpi_noise_params* p, izpi_render_stats* stats, izpi_noise_stats* noise) {
   if (!ctx) return IZPI_ERR_INVALID;
   int rc = session_usable(ctx);
@@ -241,9 +331,20 @@ int izpi_gpu_progressive_converge(izpi_ctx* ctx, const izpi_noise_params* p, izp
   izpi_noise_params q;
   if (!noise_params_ok(p, q, ctx->err) || session_lacks_noise(ctx->session, ctx->err, 0)) return IZPI_ERR_INVALID;
   HIP_TRY(hipSetDevice(ctx->device));
-  rc = converge_loop(q, ctx->session.req.spp, [&]() { return session_step(ctx, 0, nullptr); },
-                     [&](const izpi_noise_params& np, izpi_noise_stats* ns) { return session_noise(ctx, &np, ns); },
-                     [&]() { return ctx->session.done; }, noise);
+  if (ctx->session.adaptive) {  // adapt decides; the statistic after the last one is the caller's
+    izpi_adapt_stats last{};
+    bool idle = false;  // no active pixel is left: the statistic of the frame as it stands
+    rc = adapt_loop(q, ctx->session.req.spp, [&]() { return session_step(ctx, 0, nullptr); },
+                    [&](const izpi_noise_params& np, izpi_adapt_stats* as) { return session_adapt(ctx, &np, as); },
+                    [&]() { return ctx->session.done; }, &last, &idle);
+    izpi_noise_stats ns{};
+    if (!rc && (last.done || idle)) rc = session_noise(ctx, &q, &ns);
+    if (noise) *noise = ns;
+  } else {
+    rc = converge_loop(q, ctx->session.req.spp, [&]() { return session_step(ctx, 0, nullptr); },
+                       [&](const izpi_noise_params& np, izpi_noise_stats* ns) { return session_noise(ctx, &np, ns); },
+                       [&]() { return ctx->session.done; }, noise);
+  }
   if (stats) *stats = ctx->session.cum;
   return rc;
 }

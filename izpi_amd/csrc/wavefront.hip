@@ -53,22 +53,33 @@ static __global__ void k_pool_init(uint32_t* ring, uint32_t n, uint32_t per_ring
   }
 }
 
-// k_accumulate in its two instances, chosen by the parameter type: P = AccumParams is the
+// k_accumulate in its three instances, chosen by the parameter type: P = AccumParams is the
 // kernel every render runs; P = AccumMoments (AccumParams and one more pointer: AccumParams
 // itself stays as it is) is the moments instance of a session begun with IZPI_PROG_NOISE, which
 // also folds each sample's squares into `moments` ([num_pixels][3], DESIGN.md section 3.9:
 // nz::fold) in the same pass over the same bytes. The sums' additions are the same in both.
+// P = AccumScatter (AccumMoments, the active list and the counts) is the instance of an adaptive
+// session's steps after its first retirement: thread p is entry p of
+// the list, whose samples lie where pixel p's would, and adds them to the sums and moments of
+// pixel list[4 * p + 2] and chunk_spp to its count. It is never the last chunk.
 struct AccumMoments : AccumParams {
   double* moments;
+};
+struct AccumScatter : AccumMoments {
+  const uint32_t* list;  // [num_pixels][4]: (x, y, pixel, 0)
+  uint32_t* counts;
 };
 template <class P>
 static __global__ void __launch_bounds__(256) k_accumulate(const P ap) {
   constexpr bool M2 = !std::is_same<P, AccumParams>::value;
+  constexpr bool LIST = std::is_same<P, AccumScatter>::value;
   const uint32_t p = blockIdx.x * 256 + threadIdx.x;
   if (p >= ap.num_pixels) return;
-  double c0 = ap.running[3 * (size_t)p], c1 = ap.running[3 * (size_t)p + 1], c2 = ap.running[3 * (size_t)p + 2];
+  size_t at = p;  // the pixel whose sums this thread holds
+  if constexpr (LIST) at = ap.list[4 * (size_t)p + 2];
+  double c0 = ap.running[3 * at], c1 = ap.running[3 * at + 1], c2 = ap.running[3 * at + 2];
   double q0 = 0, q1 = 0, q2 = 0;
-  if constexpr (M2) { q0 = ap.moments[3 * (size_t)p]; q1 = ap.moments[3 * (size_t)p + 1]; q2 = ap.moments[3 * (size_t)p + 2]; }
+  if constexpr (M2) { q0 = ap.moments[3 * at]; q1 = ap.moments[3 * at + 1]; q2 = ap.moments[3 * at + 2]; }
   const double* s = ap.samples + (size_t)p * ap.chunk_spp * SMP_D;
   uint32_t k = 0;
   // one sample into the sums (rgb.go:36 col += ..., render/spectral.go:92-96 sum += ...);
@@ -126,9 +137,10 @@ static __global__ void __launch_bounds__(256) k_accumulate(const P ap) {
     }
   }
   for (; k < ap.chunk_spp; k++) add(s[3 * k], s[3 * k + 1], s[3 * k + 2]);  // sample order, as rgb.go:36
-  if (!ap.last) {
-    ap.running[3 * (size_t)p] = c0; ap.running[3 * (size_t)p + 1] = c1; ap.running[3 * (size_t)p + 2] = c2;
-    if constexpr (M2) { ap.moments[3 * (size_t)p] = q0; ap.moments[3 * (size_t)p + 1] = q1; ap.moments[3 * (size_t)p + 2] = q2; }
+  if (LIST || !ap.last) {
+    ap.running[3 * at] = c0; ap.running[3 * at + 1] = c1; ap.running[3 * at + 2] = c2;
+    if constexpr (M2) { ap.moments[3 * at] = q0; ap.moments[3 * at + 1] = q1; ap.moments[3 * at + 2] = q2; }
+    if constexpr (LIST) ap.counts[at] = ap.counts[at] + ap.chunk_spp;
     return;
   }
   double r0, r1, r2;
@@ -164,6 +176,12 @@ void launch_accumulate(hipStream_t st, const AccumParams& ap, double* moments) {
   } else {
     hipLaunchKernelGGL(k_accumulate<AccumParams>, grid, dim3(256), 0, st, ap);
   }
+}
+void launch_accumulate_list(hipStream_t st, const AccumParams& ap, double* moments, const uint32_t* list, uint32_t* counts) {
+  AccumScatter as;
+  static_cast<AccumParams&>(as) = ap;
+  as.moments = moments; as.list = list; as.counts = counts;
+  hipLaunchKernelGGL(k_accumulate<AccumScatter>, dim3((ap.num_pixels + 255) / 256), dim3(256), 0, st, as);
 }
 int prepare_accumulate(izpi_ctx* ctx) {
   int blocks = 0;
@@ -206,6 +224,10 @@ int run_wavefront(izpi_ctx* ctx, const izpi_render_req* req, const DevScene& sc,
   const izpi_render_tuning& tu = tuning_of(req);
   const uint32_t num_pixels = in.num_pixels, chunk = in.chunk, pool_blocks = in.pool_blocks;
   const SampleRange& sr = in.range;
+  // the samples finished before sample s of this run (an adaptive session's list: of its session)
+  auto finished_before = [&](uint32_t s) {
+    return in.list ? in.samples_before + (uint64_t)(s - sr.begin) * num_pixels : (uint64_t)s * num_pixels;
+  };
   int shade_res = 0;
   const size_t dyn = sc.lds_bytes;  // the staged tables' LDS arena (render_body)
   int rc = resident_blocks(ctx, k.shade, &shade_res, (int)SHADE_THREADS, dyn);
@@ -324,7 +346,7 @@ int run_wavefront(izpi_ctx* ctx, const izpi_render_req* req, const DevScene& sc,
       n = ctx->h_count[(3 + cur) * MISC_STRIDE];
       {  // units handed out minus the entries still queued: samples finished (a lower bound)
         const uint64_t started = std::min<uint64_t>(head, sp.total_units);
-        ctx->prog_done.store((uint64_t)s0 * num_pixels + (started > n ? started - n : 0), std::memory_order_relaxed);
+        ctx->prog_done.store(finished_before(s0) + (started > n ? started - n : 0), std::memory_order_relaxed);
       }
       if (pass_log) fprintf(stderr, "IZPI_BATCH queue %u head %u\n", n, head);
       if (head >= sp.total_units) B = 1;
@@ -348,8 +370,9 @@ int run_wavefront(izpi_ctx* ctx, const izpi_render_req* req, const DevScene& sc,
     ap.chunk_spp = cs;
     ap.raw_spectral = k.fwd && k.sampler == IZPI_SAMPLER_SPECTRAL ? 1u : 0u;
     ap.last = (!sr.keep && s0 + cs >= sr.end) ? 1u : 0u;
-    ctx->prog_done.store((uint64_t)(s0 + cs) * num_pixels, std::memory_order_relaxed);
-    launch_accumulate(st, ap, session_moments(ctx, sr));
+    ctx->prog_done.store(finished_before(s0 + cs), std::memory_order_relaxed);
+    if (in.list) launch_accumulate_list(st, ap, session_moments(ctx, sr), in.list, in.counts);
+    else launch_accumulate(st, ap, session_moments(ctx, sr));
     HIP_TRY(hipGetLastError());
   }
   return IZPI_OK;

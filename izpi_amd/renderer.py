@@ -143,6 +143,32 @@ def host_noise(sums, moment2, done, sampler=N.SAMPLER_COLOUR, counted=None, para
     return se, st.as_dict()
 
 
+def host_adapt(sums, moment2, samples, active, done, sampler=N.SAMPLER_COLOUR, counted=None, params=None):
+    """izpi_host_adapt: the host twin of one adapt() of an adaptive session over
+    (n, 3) float64 sums and second moments in packed pixel order; samples: (n,) the pixels' own
+    sample counts; active: (n,) mask of the pixels still sampled (an active pixel has `done`
+    samples); counted: as host_noise's. Returns (active after the call (n,) bool, e (n,), stats
+    dict); the arguments are not changed. Needs no GPU."""
+    sums = np.ascontiguousarray(sums, np.float64).reshape(-1, 3)
+    moment2 = np.ascontiguousarray(moment2, np.float64).reshape(-1, 3)
+    samples = np.ascontiguousarray(samples, np.uint32).reshape(-1)
+    active = np.array(active, np.uint8).reshape(-1)  # (a copy: the call writes it)
+    if sums.shape != moment2.shape or len(samples) != len(sums) or len(active) != len(sums):
+        raise ValueError("sums and moment2 are (n, 3), samples and active (n,)")
+    if counted is not None:
+        counted = np.ascontiguousarray(counted, np.uint8).reshape(-1)
+        if len(counted) != len(sums):
+            raise ValueError("counted has one entry per pixel")
+    e = np.zeros(len(sums), np.float64)
+    st = N.AdaptStats()
+    L = N.lib()
+    rc = L.izpi_host_adapt(_ptr(sums), _ptr(moment2), _ptr(counted), _ptr(samples), _ptr(active), len(sums), int(done),
+                           int(sampler), None if params is None else C.byref(params), _ptr(e), C.byref(st))
+    if rc != 0:
+        raise RuntimeError("izpi_host_adapt failed (status %d): %s" % (rc, L.izpi_host_last_error().decode()))
+    return active.astype(bool), e, st.as_dict()
+
+
 def make_request(width, height, spp, max_depth, sampler, background, seed, exposure, bg_spd=None, tiles=None,
                  layout=N.OUT_CANVAS, post=N.POST_NONE, tuning=None, accumulation=N.ACC_RECURSIVE, ink=(0.0, 0.0, 0.0)):
     """izpi_render_req for Render (the arrays it points to are kept alive on `req._keep`).
@@ -203,9 +229,15 @@ class ProgressiveSession:
     ``noise=True`` (IZPI_PROG_NOISE) also keeps the samples' second moments: ``noise()`` is
     the frame's noise statistic, ``snapshot(N.SNAP_NOISE)`` the per-pixel standard errors and
     ``converge()`` steps until the stop rule holds. The images and counters
-    are those of a session without it."""
+    are those of a session without it.
 
-    def __init__(self, owner, req, step_spp, noise=False):
+    ``adaptive=True`` (with noise=True; IZPI_PROG_ADAPTIVE): ``adapt()`` retires
+    the pixels whose estimate has fallen to the threshold, the steps sample the others only, and
+    ``snapshot(N.SNAP_SAMPLES)`` is the map of the pixels' own sample counts. Every pixel is,
+    bit for bit, that pixel of ``render(spp=its count)``. ``active``: the pixels still sampled
+    (None before the first adapt()); ``done`` stops advancing once there is none."""
+
+    def __init__(self, owner, req, step_spp, noise=False, adaptive=False):
         self._owner = owner
         self._multi = isinstance(owner, MultiGPURenderer)
         self._handle = owner.m if self._multi else owner.ctx
@@ -217,8 +249,13 @@ class ProgressiveSession:
         self.stats = None
         self._open = False
         self.noise_stats = None
+        self.adaptive = bool(adaptive)
+        self.active = None
+        self.adapt_stats = None
+        if adaptive and not noise:
+            raise ValueError("adaptive=True needs noise=True (IZPI_PROG_ADAPTIVE needs IZPI_PROG_NOISE)")
         if noise:
-            self._call("begin_ex", C.byref(req), self.step_spp, N.PROG_NOISE)
+            self._call("begin_ex", C.byref(req), self.step_spp, N.PROG_NOISE | (N.PROG_ADAPTIVE if adaptive else 0))
         else:
             self._call("begin", C.byref(req), self.step_spp)
         self._open = True
@@ -236,7 +273,8 @@ class ProgressiveSession:
         st = (N.RenderStats * G)()
         self._call("step", 0 if n is None else int(n), st)
         want = self.step_spp if n is None else int(n)
-        self.done = min(self.total, self.done + (want if want else self.step_spp))
+        if self.active != 0:  # (an adaptive session without an active pixel renders nothing)
+            self.done = min(self.total, self.done + (want if want else self.step_spp))
         self.stats = [st[i].as_dict() for i in range(G)] if self._multi else st[0].as_dict()
         self._owner.stats = self.stats
         return self.done
@@ -270,6 +308,18 @@ class ProgressiveSession:
         self.noise_stats = st.as_dict()
         return self.noise_stats
 
+    def adapt(self, params=None, **kw):
+        """izpi_gpu_progressive_adapt (an adaptive session after `done` >= 2 samples): retire
+        every active pixel that is not counted, not finite or whose e is at most the threshold.
+        Returns a dict (pixels, nonfinite, active, retired, samples, device_ms, done, converged);
+        the keywords are noise()'s."""
+        p = self._noise_params(params, kw)
+        st = N.AdaptStats()
+        self._call("adapt", None if p is None else C.byref(p), C.byref(st))
+        self.adapt_stats = st.as_dict()
+        self.active = self.adapt_stats["active"]
+        return self.adapt_stats
+
     def converge(self, params=None, **kw):
         """izpi_gpu_progressive_converge: step(step_spp) and, from max(2, min_spp) samples on,
         noise(), until the frame is converged or `done` reaches the cap. Returns the last
@@ -280,8 +330,13 @@ class ProgressiveSession:
         ns = N.NoiseStats()
         before = self.done
         self._call("converge", None if p is None else C.byref(p), st, C.byref(ns))
-        d, t = self._owner.progress()  # (pixels * done, pixels * cap)
-        self.done = d * self.total // t if t else self.done
+        if self.adaptive:  # (its progress counts the samples rendered; the last evaluation knows `done`)
+            self.done = ns.done if ns.done else self.total
+            if ns.done:
+                self.active = ns.above
+        else:
+            d, t = self._owner.progress()  # (pixels * done, pixels * cap)
+            self.done = d * self.total // t if t else self.done
         if self.done != before:
             self.stats = [st[i].as_dict() for i in range(G)] if self._multi else st[0].as_dict()
             self._owner.stats = self.stats
@@ -313,6 +368,12 @@ class ProgressiveSession:
             self.close()
         except Exception:
             pass
+
+
+def _render_adaptive(owner, threshold, step_spp, max_spp, params):
+    with owner.progressive(step_spp, total=max_spp, noise=True, adaptive=True) as s:
+        stats = s.converge(threshold=threshold, **params)
+        return s.snapshot(), stats, s.snapshot(N.SNAP_SAMPLES)[..., 0].copy()
 
 
 class GPURenderer:
@@ -419,12 +480,21 @@ class GPURenderer:
         req = self.request(tiles, layout, None, post)
         _check(N.lib().izpi_gpu_prepare(self.ctx, C.byref(req)), self.ctx, "izpi_gpu_prepare")
 
-    def progressive(self, step_spp, total=None, tiles=None, layout=N.OUT_CANVAS, post=N.POST_NONE, noise=False):
+    def progressive(self, step_spp, total=None, tiles=None, layout=N.OUT_CANVAS, post=N.POST_NONE, noise=False,
+                    adaptive=False):
         """Begin a progressive render of up to `total` samples per pixel (None: this
         renderer's spp) with a workspace sized for steps of `step_spp`: a ProgressiveSession.
         render(), prepare() and a scene upload are refused until it is closed. noise=True keeps
-        the second moments the session's noise estimate needs (24 B per pixel more)."""
-        return ProgressiveSession(self, self.request(tiles, layout, total, post), step_spp, noise)
+        the second moments the session's noise estimate needs (24 B per pixel more);
+        adaptive=True (with it) lets adapt() stop the sampling of converged pixels."""
+        return ProgressiveSession(self, self.request(tiles, layout, total, post), step_spp, noise, adaptive)
+
+    def render_adaptive(self, threshold, step_spp=16, max_spp=None, **params):
+        """render_until with adaptive sampling: a pixel stops taking samples once its own
+        estimate is at most `threshold`. Returns (canvas, stats, samples_map): every pixel of
+        the canvas is render(spp=n)'s at n = that pixel of samples_map (H, W), stats the last
+        noise statistic (None when max_spp came before the first evaluation)."""
+        return _render_adaptive(self, threshold, step_spp, max_spp, params)
 
     def render_until(self, threshold, step_spp, max_spp=None, **params):
         """Render in steps of `step_spp` until the stop rule holds at `threshold` (the other
@@ -641,12 +711,17 @@ class MultiGPURenderer:
         self.stats = [st[i].as_dict() for i in range(G)]
         return canvas if to_host else None
 
-    def progressive(self, step_spp, total=None, tiles=None, layout=N.OUT_CANVAS, post=N.POST_NONE, noise=False):
+    def progressive(self, step_spp, total=None, tiles=None, layout=N.OUT_CANVAS, post=N.POST_NONE, noise=False,
+                    adaptive=False):
         """GPURenderer.progressive over all devices: each holds a session over its share."""
         req = make_request(self.width, self.height, self.spp if total is None else int(total), self.max_depth,
                            self.sampler, self.background, self.seed, self.exposure, self._bg, tiles, layout, post,
                            self.tuning, self.accumulation, self.ink)
-        return ProgressiveSession(self, req, step_spp, noise)
+        return ProgressiveSession(self, req, step_spp, noise, adaptive)
+
+    def render_adaptive(self, threshold, step_spp=16, max_spp=None, **params):
+        """GPURenderer.render_adaptive over all devices: the same canvas and map."""
+        return _render_adaptive(self, threshold, step_spp, max_spp, params)
 
     def progress(self):
         """(samples finished, samples of the request) summed over the devices (izpi_gpu_multi_progress)."""
