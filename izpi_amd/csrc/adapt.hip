@@ -15,14 +15,6 @@ namespace {
 
 constexpr uint32_t BLOCK = 256, WAVES = BLOCK / 64;
 
-// Pixel p of the packed order sits at (x, y) of the frame (k_resolve's index rule).
-__device__ __forceinline__ void pixel_xy(const AdaptParams& a, uint32_t p, uint32_t* x, uint32_t* y) {
-  const uint32_t tile_px = a.tile_w * a.tile_h;
-  const uint32_t tile = p / tile_px, in_tile = p % tile_px;
-  *x = a.tiles[4 * tile] + in_tile % a.tile_w;
-  *y = a.tiles[4 * tile + 1] + in_tile / a.tile_w;
-}
-
 }  // namespace
 
 // One thread per session pixel in packed order. An active pixel (state 0) is evaluated at
@@ -37,22 +29,20 @@ __global__ void __launch_bounds__(BLOCK) k_adapt_select(const AdaptParams a) {
   const uint32_t t = threadIdx.x;
   const uint32_t p = blockIdx.x * BLOCK + t;
   bool keep = false, counted = false, bad = false;
-  if (p < a.num_pixels) {
+  const SessionView& v = a.view;
+  if (p < v.map.num_pixels) {
     uint32_t x, y;
-    pixel_xy(a, p, &x, &y);
+    v.map.xy(p, &x, &y);
     counted = y >= 1;
     const uint8_t s = a.state[p];
     if (s == 0) {
       double sum[3], m2[3], se[3], e;
-      for (int c = 0; c < 3; c++) {
-        sum[c] = a.running[3 * (size_t)p + c];
-        m2[c] = a.moments[3 * (size_t)p + c];
-      }
-      const bool fin = nz::pixel(sum, m2, a.done, a.sampler == IZPI_SAMPLER_SPECTRAL, a.floor, se, &e);
+      v.load(p, sum, m2);
+      const bool fin = nz::pixel(sum, m2, v.done, mean_by_reciprocal(v.sampler), a.floor, se, &e);
       keep = nz::stays_active(counted, fin, e, a.threshold);
       bad = counted && !fin;
       if (!keep) a.state[p] = bad ? 2 : 1;
-      a.counts[p] = a.done;
+      a.counts[p] = v.done;
     } else {
       bad = s == 2;
     }
@@ -113,7 +103,7 @@ __global__ void __launch_bounds__(BLOCK) k_adapt_scatter(const AdaptParams a) {
   __shared__ uint32_t wave_n[WAVES];
   const uint32_t t = threadIdx.x;
   const uint32_t p = blockIdx.x * BLOCK + t;
-  const bool keep = p < a.num_pixels && a.state[p] == 0;
+  const bool keep = p < a.view.map.num_pixels && a.state[p] == 0;
   const unsigned long long m = __ballot(keep);
   const uint32_t lane = t & 63u, wave = t >> 6;
   if (lane == 0) wave_n[wave] = __popcll(m);
@@ -122,7 +112,7 @@ __global__ void __launch_bounds__(BLOCK) k_adapt_scatter(const AdaptParams a) {
   uint32_t pos = a.block_keep[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
   for (uint32_t w = 0; w < wave; w++) pos += wave_n[w];
   uint32_t x, y;
-  pixel_xy(a, p, &x, &y);
+  a.view.map.xy(p, &x, &y);
   *reinterpret_cast<uint4*>(a.table + 4 * (size_t)pos) = make_uint4(x, y, p, 0u);
 }
 

@@ -405,10 +405,9 @@ PreviewParams preview_params(izpi_ctx* ctx, const izpi_render_req* req, const Wo
 }
 AccumParams accum_params(izpi_ctx* ctx, const izpi_render_req* req, const RequestShape& rs, double* out_dev) {
   AccumParams ap{};
-  ap.num_pixels = rs.num_pixels; ap.spp = req->spp; ap.width = req->width; ap.height = req->height;
-  ap.tile_w = rs.tw; ap.tile_h = rs.th; ap.out_layout = req->out_layout;
-  ap.sampler = rs.preview ? (uint32_t)IZPI_SAMPLER_COLOUR : req->sampler;  // (the preview samplers: col / numSamples, rgb.go:38)
-  ap.tiles = ctx->d_tiles; ap.samples = ctx->d_samples; ap.running = ctx->d_running; ap.out = out_dev;
+  ap.map = PixelMap{rs.num_pixels, req->width, req->height, rs.tw, rs.th, req->out_layout, ctx->d_tiles};
+  ap.spp = req->spp; ap.sampler = req->sampler;
+  ap.samples = ctx->d_samples; ap.running = ctx->d_running; ap.out = out_dev;
   return ap;
 }
 
@@ -475,7 +474,7 @@ int render_body(izpi_ctx* ctx, const izpi_render_req* req, const RenderCall& cal
   const uint32_t run_pixels = call.list ? call.list_count : num_pixels;
   if (call.list) {
     sp.tile_w = sp.tile_h = 1; sp.tiles = call.list;
-    ap.num_pixels = run_pixels;
+    ap.map.num_pixels = run_pixels;
   }
   if (!rs.preview) {
     path_shade_params(ctx, req, sc, rs, plan, nbg, sp);

@@ -32,6 +32,7 @@
 
 #include "izpi_dev.h"
 #include "cie_tables.h"
+#include "pixel_map.h"
 
 using namespace izd;
 
@@ -1240,10 +1241,8 @@ template <int SAMPLER, bool FWD>
 IZPI_DEV bool start_path(const DevScene& sc, const ShadeParams& sp, uint32_t unit, PathSt& P, RayRec& R) {
   const uint32_t pix_local = unit / sp.chunk_spp;
   const uint32_t s = sp.s0 + unit % sp.chunk_spp;
-  const uint32_t tile_px = sp.tile_w * sp.tile_h;
-  const uint32_t tile = pix_local / tile_px, in_tile = pix_local % tile_px;
-  const uint32_t x = sp.tiles[4 * tile] + in_tile % sp.tile_w;
-  const uint32_t y = sp.tiles[4 * tile + 1] + in_tile / sp.tile_w;
+  uint32_t x, y;
+  tile_pixel(sp.tiles, sp.tile_w, sp.tile_h, pix_local, &x, &y);
   const uint64_t key = ((uint64_t)s << 32) | (uint64_t)(y * sp.width + x);
   Lcg rng;
   rng.s = (uint32_t)splitmix64(sp.seed ^ key);
@@ -1307,10 +1306,8 @@ template <int SAMPLER>
 IZPI_DEV void camera_path(const ShadeParams& sp, uint32_t unit, PathSt& P) {
   const uint32_t pix_local = unit / sp.chunk_spp;
   const uint32_t s = sp.s0 + unit % sp.chunk_spp;
-  const uint32_t tile_px = sp.tile_w * sp.tile_h;
-  const uint32_t tile = pix_local / tile_px, in_tile = pix_local % tile_px;
-  const uint32_t x = sp.tiles[4 * tile] + in_tile % sp.tile_w;
-  const uint32_t y = sp.tiles[4 * tile + 1] + in_tile / sp.tile_w;
+  uint32_t x, y;
+  tile_pixel(sp.tiles, sp.tile_w, sp.tile_h, pix_local, &x, &y);
   const uint64_t key = ((uint64_t)s << 32) | (uint64_t)(y * sp.width + x);
   Lcg rng;
   rng.s = (uint32_t)splitmix64(sp.seed ^ key);

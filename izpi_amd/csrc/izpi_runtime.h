@@ -1,5 +1,6 @@
 // izpi_runtime.h — the host side of libizpi_gpu.so that its HIP translation units share: the
-// context, the parameter blocks of the smaller kernels, and what the units call across each other:
+// context, the parameter blocks of the smaller kernels (each embeds pixel_map.h's PixelMap, and
+// those of a session's kernels its SessionView), and what the units call across each other:
 //   izpi_gpu.hip    the context, scene upload, the buffers, the one-context render call
 //                   (render_plan.cpp: its workspace plan, plain C++);
 //   session.hip     progressive sessions on one context, their noise estimate and stop rule;
@@ -20,6 +21,7 @@
 #include "../../include/izpi_gpu_debug.h"
 #include "izpi_kern.h"
 #include "izpi_req.h"
+#include "pixel_map.h"
 #include "render_plan.h"
 
 namespace izpi_bvh {  // bvh_build.hip
@@ -29,12 +31,18 @@ int build(hipStream_t st, const double* h_boxes, uint32_t n, uint32_t leaf_max, 
 
 // ================================================================ host side (shared)
 constexpr uint32_t CPART_BLOCKS_PER_CU = 16;  // counter rows per CU / 4: above any resident 256-thread grid
+// The per-pixel kernels read where a request's pixels lie and, for a session, its sums from two
+// blocks they all embed (pixel_map.h): PixelMap, the pixels of a request in packed order and
+// their output slots, and SessionView, a session's map with its samples done, sampler, running
+// sums, second moments and per-pixel counts (session.hip builds it in one place).
 // Per-pixel sequential sum of the chunk's samples (render/rgb.go:36 col += ...,
-// render/spectral.go:164-166 sum += ...), in sample order; finalize on the last chunk.
+// render/spectral.go:164-166 sum += ...), in sample order; finalize on the last chunk
+// (pixel_mean of the request's sampler, store_pixel). An adaptive session's step over its
+// active list: map.num_pixels is the list's entries.
 struct AccumParams {
-  uint32_t num_pixels, chunk_spp, spp, width, height, tile_w, tile_h, sampler, last, out_layout;
+  PixelMap map;
+  uint32_t chunk_spp, spp, sampler, last;
   uint32_t raw_spectral;  // the samples are (radiance, lambda, pdf): weigh each (spectral_weigh) before summing
-  const uint32_t* tiles;
   const double* samples;  // [num_pixels][chunk_spp][3]
   double* running;        // [num_pixels][3]
   double* out;
@@ -47,43 +55,34 @@ struct SampleRange {
   uint32_t begin, end;
   bool keep;
 };
-// k_resolve (resolve.hip): a snapshot of the running sums after `done` samples, in the
-// layout of k_accumulate's last chunk. The sums are read only.
+// k_resolve (resolve.hip): a snapshot of the running sums after view.n(p) samples, in the
+// layout of k_accumulate's last chunk.
 struct ResolveParams {
-  uint32_t num_pixels, done, width, height, tile_w, tile_h, sampler, out_layout;
+  SessionView view;
   uint32_t form;    // IZPI_SNAP_*
   double exposure;  // IZPI_SNAP_DISPLAY of the Spectral sampler
-  const uint32_t* tiles;
-  const double* running;  // [num_pixels][3]
   double* out;
-  const uint32_t* counts;  // an adaptive session after its first retirement: n_p per pixel, used for `done`; else null
 };
 void launch_resolve(hipStream_t st, const ResolveParams& rp);
 // k_noise_resolve and k_noise_stats (noise.hip): the noise estimate of a session begun with
-// IZPI_PROG_NOISE, from its sums and second moments after `done` >= 2 samples (noise.h; DESIGN.md
-// section 3.9). Both are read only.
+// IZPI_PROG_NOISE, from its sums and second moments after view.n(p) >= 2 samples (noise.h;
+// DESIGN.md section 3.9).
 struct NoiseParams {
-  uint32_t num_pixels, done, width, height, tile_w, tile_h, sampler, out_layout;
+  SessionView view;
   double threshold, floor;  // k_noise_stats
-  const uint32_t* tiles;
-  const double* running;  // [num_pixels][3]
-  const double* moments;  // [num_pixels][3]
   double* out;            // k_noise_resolve: (se_0, se_1, se_2, 1.0) per pixel, in k_resolve's layout
   double* block_sums;     // k_noise_stats: v[0] of each 256-pixel block, [ceil(num_pixels / 256)]
   unsigned long long* block_counts;  // k_noise_stats: each block's pixels, nonfinite, above and the bits of its largest e, [blocks][4]
-  const uint32_t* counts;  // an adaptive session after its first retirement: n_p per pixel, used for `done`; else null
 };
 void launch_noise_resolve(hipStream_t st, const NoiseParams& np);
 void launch_noise_stats(hipStream_t st, const NoiseParams& np);
 // k_adapt_select, k_adapt_scan and k_adapt_scatter (adapt.hip): izpi_gpu_progressive_adapt of a
-// session begun with IZPI_PROG_ADAPTIVE (noise.h). The sums and moments are
-// read only. All arrays are the context's d_adapt (AdaptBufs).
+// session begun with IZPI_PROG_ADAPTIVE (noise.h). The rule is evaluated
+// at view.done, whatever view.counts holds; the arrays it writes are the context's d_adapt (AdaptBufs).
 struct AdaptParams {
-  uint32_t num_pixels, done, tile_w, tile_h, sampler, blocks;  // blocks = ceil(num_pixels / 256)
+  SessionView view;
+  uint32_t blocks;  // ceil(view.map.num_pixels / 256)
   double threshold, floor;
-  const uint32_t* tiles;
-  const double* running;  // [num_pixels][3]
-  const double* moments;  // [num_pixels][3]
   uint32_t* counts;       // [num_pixels]: n_p, the samples in pixel p's sums
   uint8_t* state;         // [num_pixels]: 0 active, 1 retired, 2 retired as a counted non-finite pixel
   uint32_t* table;        // [num_pixels][4]: the active list in packed order, (x, y, pixel, 0) per entry: the 1 x 1 tiles of a step

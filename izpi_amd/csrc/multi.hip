@@ -10,25 +10,15 @@
 
 using namespace izpi_internal;
 
-// Packed pixel p (IZPI_OUT_PACKED: tile after tile, the rows of each tile) -> its canvas
-// column x and row H - y (rgb.go:41); false for sample row y = 0, which has no canvas row.
-// k_unpack and izpi_host_assemble_shares share this rule.
-__host__ __device__ inline bool packed_target(const uint32_t* tiles, uint32_t p, uint32_t tile_w, uint32_t tile_h,
-                                              uint32_t height, uint32_t* x, uint32_t* row) {
-  const uint32_t tile_px = tile_w * tile_h;
-  const uint32_t tile = p / tile_px, in_tile = p % tile_px;
-  *x = tiles[4 * tile] + in_tile % tile_w;
-  *row = height - (tiles[4 * tile + 1] + in_tile / tile_w);
-  return *row < height;
-}
+// Packed pixel p of the tiles (IZPI_OUT_PACKED) into its slot of the W x H canvas (PixelMap::slot,
+// pixel_map.h; sample row y = 0 has none), as izpi_host_assemble_shares does on the host.
 __global__ void k_unpack(const uint32_t* tiles, uint32_t num_pixels, uint32_t tile_w, uint32_t tile_h, uint32_t width,
                          uint32_t height, const double* packed, double* canvas) {
   const uint32_t p = blockIdx.x * 256 + threadIdx.x;
   if (p >= num_pixels) return;
-  uint32_t x, row;
-  if (packed_target(tiles, p, tile_w, tile_h, height, &x, &row)) {
+  const PixelMap map{num_pixels, width, height, tile_w, tile_h, IZPI_OUT_CANVAS, tiles};
+  if (double* o = map.slot(p, canvas)) {
     const double* s = packed + (size_t)p * 4;
-    double* o = canvas + ((size_t)row * width + x) * 4;
     o[0] = s[0]; o[1] = s[1]; o[2] = s[2]; o[3] = s[3];
   }
 }
@@ -702,11 +692,9 @@ int izpi_host_assemble_shares(uint32_t width, uint32_t height, const uint32_t* t
   for (uint32_t r = 0; r < num_shares; r++) {
     const uint32_t nt = izpi_host_share_tiles(tiles, num_tiles, r, num_shares, mine.data());
     const double* packed = gathered + (size_t)r * block;
-    for (uint32_t p = 0; p < nt * tw * th; p++) {
-      uint32_t x, row;
-      if (packed_target(mine.data(), p, tw, th, height, &x, &row))
-        memcpy(canvas + ((size_t)row * width + x) * 4, packed + (size_t)p * 4, 4 * sizeof(double));
-    }
+    const PixelMap map{nt * tw * th, width, height, tw, th, IZPI_OUT_CANVAS, mine.data()};
+    for (uint32_t p = 0; p < map.num_pixels; p++)
+      if (double* o = map.slot(p, canvas)) memcpy(o, packed + (size_t)p * 4, 4 * sizeof(double));
   }
   return IZPI_OK;
 }

@@ -7,49 +7,16 @@
 #include "izpi_runtime.h"
 #include "noise.h"
 
-namespace {
-
-// Pixel p's sums and moments (48 B).
-__device__ __forceinline__ void load_pixel(const NoiseParams& np, uint32_t p, double s[3], double m2[3]) {
-  for (int c = 0; c < 3; c++) {
-    s[c] = np.running[3 * (size_t)p + c];
-    m2[c] = np.moments[3 * (size_t)p + c];
-  }
-}
-
-// Pixel p of the packed order sits at (x, y) of the frame (k_resolve's index rule).
-__device__ __forceinline__ void pixel_xy(const NoiseParams& np, uint32_t p, uint32_t* x, uint32_t* y) {
-  const uint32_t tile_px = np.tile_w * np.tile_h;
-  const uint32_t tile = p / tile_px, in_tile = p % tile_px;
-  *x = np.tiles[4 * tile] + in_tile % np.tile_w;
-  *y = np.tiles[4 * tile + 1] + in_tile / np.tile_w;
-}
-
-// The samples in pixel p's sums: an adaptive session's own count once a pixel has retired
-// (DESIGN.md section 3.10), else the session's.
-__device__ __forceinline__ uint32_t pixel_n(const NoiseParams& np, uint32_t p) { return np.counts ? np.counts[p] : np.done; }
-
-}  // namespace
-
 // One thread per pixel in packed order: 48 B of sums and moments in, 32 B out; HBM-streaming.
 // Writes (se_0, se_1, se_2, 1.0) where k_resolve writes the pixel.
 __global__ void __launch_bounds__(256) k_noise_resolve(const NoiseParams np) {
+  const SessionView& v = np.view;
   const uint32_t p = blockIdx.x * 256 + threadIdx.x;
-  if (p >= np.num_pixels) return;
+  if (p >= v.map.num_pixels) return;
   double s[3], m2[3], se[3], e;
-  load_pixel(np, p, s, m2);
-  nz::pixel(s, m2, pixel_n(np, p), np.sampler == IZPI_SAMPLER_SPECTRAL, np.floor, se, &e);
-  double* o;
-  if (np.out_layout == IZPI_OUT_PACKED) {
-    o = np.out + (size_t)p * 4;
-  } else {  // canvas.Set(x, ny - y), row ny is dropped (A9)
-    uint32_t x, y;
-    pixel_xy(np, p, &x, &y);
-    const uint32_t row = np.height - y;
-    if (row >= np.height) return;
-    o = np.out + ((size_t)row * np.width + x) * 4;
-  }
-  o[0] = se[0]; o[1] = se[1]; o[2] = se[2]; o[3] = 1.0;
+  v.load(p, s, m2);
+  nz::pixel(s, m2, v.n(p), mean_by_reciprocal(v.sampler), np.floor, se, &e);
+  store_pixel(v.map, p, np.out, se[0], se[1], se[2]);
 }
 
 // The frame statistic: one thread per pixel in packed order, blocks of nz::BLOCK = 256 = four
@@ -68,13 +35,14 @@ __global__ void __launch_bounds__(nz::BLOCK) k_noise_stats(const NoiseParams np)
   const uint32_t p = blockIdx.x * nz::BLOCK + t;
   bool counted = false, fin = false;
   double e = 0.0;
-  if (p < np.num_pixels) {
+  const SessionView& sv = np.view;
+  if (p < sv.map.num_pixels) {
     uint32_t x, y;
-    pixel_xy(np, p, &x, &y);
+    sv.map.xy(p, &x, &y);
     counted = y >= 1;
     double s[3], m2[3], se[3];
-    load_pixel(np, p, s, m2);
-    fin = nz::pixel(s, m2, pixel_n(np, p), np.sampler == IZPI_SAMPLER_SPECTRAL, np.floor, se, &e);
+    sv.load(p, s, m2);
+    fin = nz::pixel(s, m2, sv.n(p), mean_by_reciprocal(sv.sampler), np.floor, se, &e);
   }
   const bool good = counted && fin;
   const double mine = good ? e : 0.0;
@@ -108,8 +76,8 @@ __global__ void __launch_bounds__(nz::BLOCK) k_noise_stats(const NoiseParams np)
 }
 
 void launch_noise_resolve(hipStream_t st, const NoiseParams& np) {
-  hipLaunchKernelGGL(k_noise_resolve, dim3((np.num_pixels + 255) / 256), dim3(256), 0, st, np);
+  hipLaunchKernelGGL(k_noise_resolve, dim3((np.view.map.num_pixels + 255) / 256), dim3(256), 0, st, np);
 }
 void launch_noise_stats(hipStream_t st, const NoiseParams& np) {
-  hipLaunchKernelGGL(k_noise_stats, dim3((np.num_pixels + nz::BLOCK - 1) / nz::BLOCK), dim3(nz::BLOCK), 0, st, np);
+  hipLaunchKernelGGL(k_noise_stats, dim3((np.view.map.num_pixels + nz::BLOCK - 1) / nz::BLOCK), dim3(nz::BLOCK), 0, st, np);
 }

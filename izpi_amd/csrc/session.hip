@@ -49,16 +49,23 @@ static AdaptParams adapt_arrays(izpi_ctx* ctx) {
   const izpi_ctx::Session& ss = ctx->session;
   const AdaptBufs ab(ss.num_pixels);
   AdaptParams a{};
-  a.num_pixels = ss.num_pixels; a.blocks = (ss.num_pixels + 255) / 256;
+  a.blocks = (ss.num_pixels + 255) / 256;
   a.table = (uint32_t*)(ctx->d_adapt + ab.table); a.counts = (uint32_t*)(ctx->d_adapt + ab.counts);
   a.block_keep = (uint32_t*)(ctx->d_adapt + ab.block_keep); a.block_stat = (uint32_t*)(ctx->d_adapt + ab.block_stat);
   a.totals = (uint32_t*)(ctx->d_adapt + ab.totals); a.state = (uint8_t*)(ctx->d_adapt + ab.state);
   return a;
 }
-// The per-pixel counts the snapshots and the statistic read: an adaptive session's once a pixel
-// has retired; until then every pixel has `done` samples, and the plain forms run.
-static const uint32_t* session_counts(izpi_ctx* ctx) {
-  return ctx->session.listed ? adapt_arrays(ctx).counts : nullptr;
+// The session's sums as its per-pixel kernels read them (SessionView, pixel_map.h), over the
+// tiles session_tiles puts in d_tiles. The per-pixel counts are an adaptive session's once a
+// pixel has retired; until then every pixel has `done` samples, and the plain forms run.
+static SessionView session_view(izpi_ctx* ctx) {
+  const izpi_ctx::Session& ss = ctx->session;
+  SessionView v{};
+  v.map = PixelMap{ss.num_pixels, ss.req.width, ss.req.height, ss.tile_w, ss.tile_h, ss.req.out_layout, ctx->d_tiles};
+  v.done = ss.done; v.sampler = ss.req.sampler;
+  v.running = ctx->d_running; v.moments = ctx->d_moments;
+  v.counts = ss.listed ? adapt_arrays(ctx).counts : nullptr;
+  return v;
 }
 // IZPI_PROG_ADAPTIVE: every pixel active with no sample, in a buffer of its own.
 static int session_zero_adapt(izpi_ctx* ctx) {
@@ -177,16 +184,6 @@ bool session_lacks_adaptive(const izpi_ctx::Session& ss, std::string& err) {
   if (!ss.adaptive) err = "adapt: the session was begun without IZPI_PROG_ADAPTIVE";
   return !ss.adaptive;
 }
-static NoiseParams noise_params(izpi_ctx* ctx) {
-  const izpi_ctx::Session& ss = ctx->session;
-  NoiseParams np{};
-  np.num_pixels = ss.num_pixels; np.done = ss.done; np.width = ss.req.width; np.height = ss.req.height;
-  np.tile_w = ss.tile_w; np.tile_h = ss.tile_h; np.sampler = ss.req.sampler; np.out_layout = ss.req.out_layout;
-  np.threshold = IZPI_NOISE_DEFAULT_THRESHOLD; np.floor = IZPI_NOISE_DEFAULT_FLOOR;
-  np.tiles = ctx->d_tiles; np.running = ctx->d_running; np.moments = ctx->d_moments;
-  np.counts = session_counts(ctx);
-  return np;
-}
 
 // noise: k_noise_stats over the sums and moments; the block sums are added here, in block order.
 int session_noise(izpi_ctx* ctx, const izpi_noise_params* params, izpi_noise_stats* out) {
@@ -199,7 +196,8 @@ int session_noise(izpi_ctx* ctx, const izpi_noise_params* params, izpi_noise_sta
   if ((rc = session_tiles(ctx))) return rc;
   const size_t blocks = ((size_t)ss.num_pixels + nz::BLOCK - 1) / nz::BLOCK;
   if ((rc = grow(ctx, (void**)&ctx->d_noisepart, &ctx->noisepart_cap, 5 * blocks * sizeof(double)))) return rc;
-  NoiseParams np = noise_params(ctx);
+  NoiseParams np{};
+  np.view = session_view(ctx);
   np.threshold = p.threshold; np.floor = p.floor;
   np.block_sums = ctx->d_noisepart;
   np.block_counts = (unsigned long long*)(ctx->d_noisepart + blocks);
@@ -241,9 +239,8 @@ int session_adapt(izpi_ctx* ctx, const izpi_noise_params* params, izpi_adapt_sta
   hipStream_t st = ctx->stream;
   if ((rc = session_tiles(ctx))) return rc;
   AdaptParams a = adapt_arrays(ctx);
-  a.done = ss.done; a.tile_w = ss.tile_w; a.tile_h = ss.tile_h; a.sampler = ss.req.sampler;
+  a.view = session_view(ctx);
   a.threshold = p.threshold; a.floor = p.floor;
-  a.tiles = ctx->d_tiles; a.running = ctx->d_running; a.moments = ctx->d_moments;
   HIP_TRY(hipEventRecord(ctx->ev0, st));
   launch_adapt(st, a);
   HIP_TRY(hipGetLastError());
@@ -276,7 +273,9 @@ int session_snapshot(izpi_ctx* ctx, uint32_t form, double* out_dev) {
   hipStream_t st = ctx->stream;
   if ((rc = session_tiles(ctx))) return rc;
   if (form == IZPI_SNAP_NOISE) {  // k_noise_resolve: the standard errors, where k_resolve writes the pixels; no post
-    NoiseParams np = noise_params(ctx);
+    NoiseParams np{};
+    np.view = session_view(ctx);
+    np.floor = IZPI_NOISE_DEFAULT_FLOOR;  // (of e, which the snapshot does not show)
     np.out = out_dev;
     launch_noise_resolve(st, np);
     HIP_TRY(hipGetLastError());
@@ -284,11 +283,8 @@ int session_snapshot(izpi_ctx* ctx, uint32_t form, double* out_dev) {
     return IZPI_OK;
   }
   ResolveParams rp{};
-  rp.num_pixels = ss.num_pixels; rp.done = ss.done; rp.width = ss.req.width; rp.height = ss.req.height;
-  rp.tile_w = ss.tile_w; rp.tile_h = ss.tile_h; rp.sampler = ss.req.sampler; rp.out_layout = ss.req.out_layout;
-  rp.form = form; rp.exposure = ss.req.exposure;
-  rp.tiles = ctx->d_tiles; rp.running = ctx->d_running; rp.out = out_dev;
-  rp.counts = session_counts(ctx);
+  rp.view = session_view(ctx);
+  rp.form = form; rp.exposure = ss.req.exposure; rp.out = out_dev;
   launch_resolve(st, rp);
   HIP_TRY(hipGetLastError());
   if (form == IZPI_SNAP_CANVAS && (rc = apply_post(ctx, &ss.req, out_dev))) return rc;

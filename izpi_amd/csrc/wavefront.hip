@@ -74,7 +74,7 @@ static __global__ void __launch_bounds__(256) k_accumulate(const P ap) {
   constexpr bool M2 = !std::is_same<P, AccumParams>::value;
   constexpr bool LIST = std::is_same<P, AccumScatter>::value;
   const uint32_t p = blockIdx.x * 256 + threadIdx.x;
-  if (p >= ap.num_pixels) return;
+  if (p >= ap.map.num_pixels) return;
   size_t at = p;  // the pixel whose sums this thread holds
   if constexpr (LIST) at = ap.list[4 * (size_t)p + 2];
   double c0 = ap.running[3 * at], c1 = ap.running[3 * at + 1], c2 = ap.running[3 * at + 2];
@@ -95,7 +95,7 @@ static __global__ void __launch_bounds__(256) k_accumulate(const P ap) {
       if constexpr (M2) nz::fold(a, b, c, q0, q1, q2);
     }
   };
-  if ( (ap.chunk_spp & 3u) == 0 && blockIdx.x * 256 + 256 <= ap.num_pixels) {
+  if ( (ap.chunk_spp & 3u) == 0 && blockIdx.x * 256 + 256 <= ap.map.num_pixels) {
     // Staged through LDS, 4 samples (96 B) of each of the wave's 64 pixels at a time: the
     // wave's lanes load the 64 runs as consecutive 16-B pieces (a load instruction covers
     // ~11 neighbouring runs instead of one piece of 64 runs 12 KB apart), then each lane
@@ -143,31 +143,13 @@ static __global__ void __launch_bounds__(256) k_accumulate(const P ap) {
     if constexpr (LIST) ap.counts[at] = ap.counts[at] + ap.chunk_spp;
     return;
   }
-  double r0, r1, r2;
-  if (ap.sampler == IZPI_SAMPLER_COLOUR) {  // vec3.ScalarDiv(col, numSamples)
-    r0 = c0 / (double)ap.spp; r1 = c1 / (double)ap.spp; r2 = c2 / (double)ap.spp;
-  } else {  // sum * (1/numSamples)
-    const double inv = 1.0 / (double)ap.spp;
-    r0 = c0 * inv; r1 = c1 * inv; r2 = c2 * inv;
-  }
-  const uint32_t tile_px = ap.tile_w * ap.tile_h;
-  if (ap.out_layout == IZPI_OUT_PACKED) {
-    double* o = ap.out + (size_t)p * 4;
-    o[0] = r0; o[1] = r1; o[2] = r2; o[3] = 1.0;
-    return;
-  }
-  const uint32_t tile = p / tile_px, in_tile = p % tile_px;
-  const uint32_t x = ap.tiles[4 * tile] + in_tile % ap.tile_w;
-  const uint32_t y = ap.tiles[4 * tile + 1] + in_tile / ap.tile_w;
-  const uint32_t row = ap.height - y;  // canvas.Set(x, ny-y): row ny is dropped (A9)
-  if (row < ap.height) {
-    double* o = ap.out + ((size_t)row * ap.width + x) * 4;
-    o[0] = r0; o[1] = r1; o[2] = r2; o[3] = 1.0;
-  }
+  // the last chunk: the request's mean into the pixel's slot (pixel_map.h)
+  store_pixel(ap.map, p, ap.out, pixel_mean(ap.sampler, c0, ap.spp), pixel_mean(ap.sampler, c1, ap.spp),
+              pixel_mean(ap.sampler, c2, ap.spp));
 }
 
 void launch_accumulate(hipStream_t st, const AccumParams& ap, double* moments) {
-  const dim3 grid((ap.num_pixels + 255) / 256);
+  const dim3 grid((ap.map.num_pixels + 255) / 256);
   if (moments) {
     AccumMoments am;
     static_cast<AccumParams&>(am) = ap;
@@ -181,7 +163,7 @@ void launch_accumulate_list(hipStream_t st, const AccumParams& ap, double* momen
   AccumScatter as;
   static_cast<AccumParams&>(as) = ap;
   as.moments = moments; as.list = list; as.counts = counts;
-  hipLaunchKernelGGL(k_accumulate<AccumScatter>, dim3((ap.num_pixels + 255) / 256), dim3(256), 0, st, as);
+  hipLaunchKernelGGL(k_accumulate<AccumScatter>, dim3((ap.map.num_pixels + 255) / 256), dim3(256), 0, st, as);
 }
 int prepare_accumulate(izpi_ctx* ctx) {
   int blocks = 0;
