@@ -28,6 +28,15 @@ int izpi_gpu_debug_fault(izpi_ctx* ctx, int where);
  * (every render rewrites them). */
 int izpi_gpu_debug_realloc(izpi_ctx* ctx, uint32_t mask);
 
+/* k_trace2's global-memory box test on n (node, ray) pairs: boxes[n][24] are a node's bounds in
+ * GInner's order (mnx[4], mny[4], mnz[4], mxx[4], mxy[4], mxz[4]), rays[n][7] the f32 origin,
+ * inverse direction and tMax, as izpi_gpu_ray_aabb4 takes them; masks[i] bit k = slot k is hit.
+ * The pairs run a lane each, in whole waves, through the kernel's own functions: the near-plane
+ * index by the ray's sign, the planes picked by it and the sorted four-slot test; a wave with a
+ * ray or box the sorted test is not exact for (a zero, infinite or NaN ray component; a NaN or
+ * inverted bound) runs the scalar twin on those planes. */
+int izpi_gpu_debug_slab4(izpi_ctx* ctx, const float* boxes, const float* rays, uint32_t n, uint8_t* masks);
+
 #ifdef __cplusplus
 }
 #endif

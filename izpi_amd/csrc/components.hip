@@ -138,6 +138,40 @@ __global__ void k_aabb4(const float* boxes, const float* rays, uint32_t n, uint8
   masks[i] = m;
 }
 
+// k_trace2's global-memory box test on n (node, ray) pairs, a lane each, in whole waves: the
+// near-index rule, the planes selected by it and slab4_sorted for a wave of fast rays, the twin on
+// those same planes for a wave that holds any other ray (as the node step chooses).
+__global__ void k_debug_slab4(const float* boxes, const float* rays, uint32_t n, uint8_t* masks) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  const uint32_t j = i < n ? i : n - 1;  // (n > 0; the lanes past n repeat the last pair)
+  const float* b = boxes + (size_t)j * 24;
+  const float* r = rays + (size_t)j * 7;
+  const float ox = r[0], oy = r[1], oz = r[2], ix = r[3], iy = r[4], iz = r[5], tm = r[6];
+  // (the upload facts nan_free_bounds and ordered_bounds, here of the pair's own box)
+  bool box_ok = true;
+  for (int k = 0; k < 4; k++) box_ok = box_ok && b[k] <= b[12 + k] && b[4 + k] <= b[16 + k] && b[8 + k] <= b[20 + k];
+  const bool fast = box_ok && ray_fast_ok(ox, oy, oz, ix, iy, iz);
+  const uint32_t nx = slab_near_index(0, ix, fast), ny = slab_near_index(1, iy, fast), nz = slab_near_index(2, iz, fast);
+  auto plane = [&](uint32_t k) { return make_float4(b[4 * k], b[4 * k + 1], b[4 * k + 2], b[4 * k + 3]); };
+  const float4 p0 = plane(nx), p1 = plane(ny), p2 = plane(nz);
+  const float4 p3 = plane(slab_far_index(0, nx)), p4 = plane(slab_far_index(1, ny)), p5 = plane(slab_far_index(2, nz));
+  uint64_t hit[4];
+  if (__builtin_amdgcn_ballot_w64(!fast) == 0) {
+    slab4_sorted(p0, p1, p2, p3, p4, p5, ox, oy, oz, ix, iy, iz, tm, hit);
+  } else {
+    const float a0[4] = {p0.x, p0.y, p0.z, p0.w}, a1[4] = {p1.x, p1.y, p1.z, p1.w}, a2[4] = {p2.x, p2.y, p2.z, p2.w},
+                a3[4] = {p3.x, p3.y, p3.z, p3.w}, a4[4] = {p4.x, p4.y, p4.z, p4.w}, a5[4] = {p5.x, p5.y, p5.z, p5.w};
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+      hit[k] = __builtin_amdgcn_ballot_w64(slab(a0[k], a1[k], a2[k], a3[k], a4[k], a5[k], ox, oy, oz, ix, iy, iz, tm));
+  }
+  const uint32_t lane = threadIdx.x & 63;
+  uint8_t m = 0;
+#pragma unroll
+  for (int k = 0; k < 4; k++) m |= (uint8_t)(((hit[k] >> lane) & 1u) << k);
+  if (i < n) masks[i] = m;
+}
+
 __global__ void k_gomath(const DevScene sc, int op, const double* x, const double* y, uint32_t n, double* out) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
@@ -330,6 +364,24 @@ int izpi_gpu_ray_aabb4(izpi_ctx* ctx, const float* boxes, const float* rays, uin
   HIP_TRY(hipMemcpy(db, boxes, (size_t)n * 24 * sizeof(float), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(dr, rays, (size_t)n * 7 * sizeof(float), hipMemcpyHostToDevice));
   hipLaunchKernelGGL(k_aabb4, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, db, dr, n, dm);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  HIP_TRY(hipMemcpy(masks, dm, n, hipMemcpyDeviceToHost));
+  return IZPI_OK;
+}
+
+int izpi_gpu_debug_slab4(izpi_ctx* ctx, const float* boxes, const float* rays, uint32_t n, uint8_t* masks) {
+  if (!ctx || !boxes || !rays || !masks) return IZPI_ERR_INVALID;
+  if (n == 0) return IZPI_OK;
+  HIP_TRY(hipSetDevice(ctx->device));
+  DevBufs tmp;  // freed on every return
+  float *db, *dr; uint8_t* dm;
+  HIP_TRY(tmp.alloc(&db, (size_t)n * 24));
+  HIP_TRY(tmp.alloc(&dr, (size_t)n * 7));
+  HIP_TRY(tmp.alloc(&dm, n));
+  HIP_TRY(hipMemcpy(db, boxes, (size_t)n * 24 * sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dr, rays, (size_t)n * 7 * sizeof(float), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_debug_slab4, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, db, dr, n, dm);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   HIP_TRY(hipMemcpy(masks, dm, n, hipMemcpyDeviceToHost));

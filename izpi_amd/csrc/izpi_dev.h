@@ -7,6 +7,7 @@
 #include "../../include/izpi_gpu.h"
 #include "gomath.h"
 #include "scene_records.h"
+#include "slab_rule.h"
 
 #define IZPI_DEV __device__ __forceinline__
 
@@ -46,6 +47,8 @@ struct DevScene {
                                 // k_trace2 addresses their records by 32-bit byte offsets (fills the struct's tail padding)
   uint32_t leaf_max;            // the largest primitive count of a leaf, 0 for an empty scene (make_tracer: at most 3, as
                                 // the GPU builder's trees have, picks the primitive step sized for three)
+  uint32_t ordered_bounds;      // mn <= mx on every axis of every valid slot and leaf box: with nan_free_bounds,
+                                // k_trace2 picks a fast ray's near and far planes by its sign (slab4_sorted; fills the tail padding)
 #ifdef IZPI_SHADOW
   // measurement builds only (byte breakdown): copies of the traversal arrays that
   // k_trace2 reads beside the real ones, so a class's bytes past L2 show as extra FETCH_SIZE
@@ -194,21 +197,7 @@ IZPI_DEV V3 random_in_unit_sphere(Lcg& r) {
 }
 
 // --------------------------------------------------- RayAABB4 (bvh4_simd_generic.go)
-// Comparisons written as the scalar twin's select form: never fminf/fmaxf (A14).
-IZPI_DEV float max32(float a, float b) { return a > b ? a : b; }
-IZPI_DEV float min32(float a, float b) { return a < b ? a : b; }
-IZPI_DEV bool slab(float mnx, float mny, float mnz, float mxx, float mxy, float mxz, float ox, float oy, float oz,
-                   float ix, float iy, float iz, float tmax) {
-  float t0x = (mnx - ox) * ix, t1x = (mxx - ox) * ix;
-  if (t0x > t1x) { float t = t0x; t0x = t1x; t1x = t; }
-  float t0y = (mny - oy) * iy, t1y = (mxy - oy) * iy;
-  if (t0y > t1y) { float t = t0y; t0y = t1y; t1y = t; }
-  float t0z = (mnz - oz) * iz, t1z = (mxz - oz) * iz;
-  if (t0z > t1z) { float t = t0z; t0z = t1z; t1z = t; }
-  float tn = max32(max32(t0x, t0y), t0z);
-  float tf = min32(min32(t1x, t1y), t1z);
-  return tn <= tf && tf >= 0 && tn <= tmax;
-}
+// The scalar twin `slab`, ray_fast_ok and the per-slot sorted rule are in slab_rule.h.
 
 // RayAABB4 over the 4 slots of an inner node, NaN-free fast form. When the ray's f32
 // origin is finite and its f32 inverse direction is finite and non-zero on every axis,
@@ -244,11 +233,28 @@ IZPI_DEV void slab4_fast(float4 mnx, float4 mny, float4 mnz, float4 mxx, float4 
     h[i] = __builtin_amdgcn_ballot_w64(tn <= tf) & __builtin_amdgcn_ballot_w64(tf >= 0.0f) & __builtin_amdgcn_ballot_w64(tn <= tmax);
   }
 }
-IZPI_DEV bool ray_fast_ok(float ox, float oy, float oz, float ix, float iy, float iz) {
-  const float inf = __builtin_huge_valf();
-  return __builtin_fabsf(ox) < inf && __builtin_fabsf(oy) < inf && __builtin_fabsf(oz) < inf &&
-         __builtin_fabsf(ix) < inf && __builtin_fabsf(iy) < inf && __builtin_fabsf(iz) < inf &&
-         ix != 0.0f && iy != 0.0f && iz != 0.0f;
+// The same test for the planes already chosen by the ray's sign (slab_rule.h: near / far hold, per
+// slot, the near and far plane of each axis): no sort of the two products. Exact for a fast ray
+// (ray_fast_ok) on NaN-free bounds with mn <= mx (DevScene::ordered_bounds). The three compares are
+// slab_sorted_hit's, each with a ballot of its own, as in slab4_fast.
+IZPI_DEV void slab4_sorted(float4 nrx, float4 nry, float4 nrz, float4 frx, float4 fry, float4 frz, float ox, float oy,
+                           float oz, float ix, float iy, float iz, float tmax, uint64_t (&h)[4]) {
+  const f32x2 o_x = {ox, ox}, o_y = {oy, oy}, o_z = {oz, oz};
+  const f32x2 i_x = {ix, ix}, i_y = {iy, iy}, i_z = {iz, iz};
+  const f32x2 a0x = (f32x2{nrx.x, nrx.y} - o_x) * i_x, a1x = (f32x2{nrx.z, nrx.w} - o_x) * i_x;
+  const f32x2 b0x = (f32x2{frx.x, frx.y} - o_x) * i_x, b1x = (f32x2{frx.z, frx.w} - o_x) * i_x;
+  const f32x2 a0y = (f32x2{nry.x, nry.y} - o_y) * i_y, a1y = (f32x2{nry.z, nry.w} - o_y) * i_y;
+  const f32x2 b0y = (f32x2{fry.x, fry.y} - o_y) * i_y, b1y = (f32x2{fry.z, fry.w} - o_y) * i_y;
+  const f32x2 a0z = (f32x2{nrz.x, nrz.y} - o_z) * i_z, a1z = (f32x2{nrz.z, nrz.w} - o_z) * i_z;
+  const f32x2 b0z = (f32x2{frz.x, frz.y} - o_z) * i_z, b1z = (f32x2{frz.z, frz.w} - o_z) * i_z;
+  const float nx[4] = {a0x.x, a0x.y, a1x.x, a1x.y}, fx[4] = {b0x.x, b0x.y, b1x.x, b1x.y};
+  const float ny[4] = {a0y.x, a0y.y, a1y.x, a1y.y}, fy[4] = {b0y.x, b0y.y, b1y.x, b1y.y};
+  const float nz[4] = {a0z.x, a0z.y, a1z.x, a1z.y}, fz[4] = {b0z.x, b0z.y, b1z.x, b1z.y};
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const float tn = slab_sorted_near(nx[i], ny[i], nz[i]), tf = slab_sorted_far(fx[i], fy[i], fz[i]);
+    h[i] = __builtin_amdgcn_ballot_w64(tn <= tf) & __builtin_amdgcn_ballot_w64(tf >= 0.0f) & __builtin_amdgcn_ballot_w64(tn <= tmax);
+  }
 }
 
 // ----------------------------------------------------- primitive tests

@@ -601,7 +601,7 @@ int upload_packed(izpi_ctx* ctx, const izpi_scene_desc* d, const PackedScene& ps
      // their own. (UP with no host array only allocates: the three parts are copied below.)
     const TraceLayout tl = trace_layout(ps.inner.size(), ps.innerq.size(), ps.leaves.size());
     char* nb;
-    UP((const char*)nullptr, tl.bytes, &nb);
+    UP((const char*)nullptr, tl.alloc_bytes, &nb);
     di = reinterpret_cast<GInner*>(nb);
     dq = ps.innerq.empty() ? nullptr : reinterpret_cast<GInnerQ*>(nb + tl.innerq_at);
     dl = reinterpret_cast<GLeaf*>(nb + tl.leaves_at);
@@ -635,6 +635,7 @@ int upload_packed(izpi_ctx* ctx, const izpi_scene_desc* d, const PackedScene& ps
   sc.spd_wl = dswl; sc.spd_val = dsv;
   sc.root = ps.root; sc.num_inner = ps.num_inner; sc.num_prims = d->num_prims; sc.num_lights = d->num_lights;
   sc.quantized = ps.quantized; sc.leaf_shortcut = ps.leaf_shortcut; sc.nan_free_bounds = ps.nan_free_bounds;
+  sc.ordered_bounds = ps.ordered_bounds;
   sc.tri_only = ps.tri_only; sc.time_free = ps.time_free; sc.no_pathlen = ps.no_pathlen; sc.leaf_max = ps.leaf_max;
   sc.addr32 = trace_addr32(ps.inner.size(), ps.innerq.size(), ps.leaves.size(), ps.prims.size());
   sc.cam = d->camera;

@@ -435,6 +435,14 @@ void scene_flags(const izpi_scene_desc* d, PackedScene* out) {
   }
   for (const GLeaf& L : out->leaves)  // leaf re-tests run through the same 4-slot test
     for (int i = 0; i < 3; i++) if (L.mn[i] != L.mn[i] || L.mx[i] != L.mx[i]) out->nan_free_bounds = 0;
+  // ordered_bounds: mn <= mx on every axis of every valid slot and of every leaf box (an empty
+  // slot's box is read by no sorted test's result: k_trace2 masks it by its child)
+  out->ordered_bounds = 1;
+  for (const GInner& g : out->inner)
+    for (int i = 0; i < 4; i++)
+      if (g.child[i] != -1 && !(g.mnx[i] <= g.mxx[i] && g.mny[i] <= g.mxy[i] && g.mnz[i] <= g.mxz[i])) out->ordered_bounds = 0;
+  for (const GLeaf& L : out->leaves)
+    for (int i = 0; i < 3; i++) if (!(L.mn[i] <= L.mx[i])) out->ordered_bounds = 0;
 }
 
 }  // namespace

@@ -32,7 +32,7 @@ struct PackedScene {
   std::vector<double> texels;            // >= 1, every image texture's own run (TexSlot)
   // DevScene's scalars
   int32_t root = -1;
-  uint32_t num_inner = 0, leaf_shortcut = 1, quantized = 0, nan_free_bounds = 1, time_free = 1, no_pathlen = 1, tri_only = 1;
+  uint32_t num_inner = 0, leaf_shortcut = 1, quantized = 0, nan_free_bounds = 1, ordered_bounds = 1, time_free = 1, no_pathlen = 1, tri_only = 1;
   uint32_t stack_needed = 0;             // stack_bound of the tree
   uint32_t leaf_max = 0;                 // the largest primitive count of a leaf (0: no leaf)
   // what the materials allow and need: the kernel instances a render picks
@@ -48,12 +48,16 @@ int pack_scene(const izpi_scene_desc* d, PackedScene* out, std::string* err);
 
 // The node block of an uploaded scene: the inner nodes at its start, then their quantised form
 // (if any), then the leaf records, in one device allocation (byte offsets; counts of records).
-struct TraceLayout { uint64_t innerq_at, leaves_at, bytes; };
+// alloc_bytes: the allocation, TRACE_TAIL_PAD past the records: a leaf lane of k_trace2 loads 16 B at each
+// of its box's six floats (GLeaf::mn, mx), so the load at the last record's mx[2] ends 4 B past it.
+constexpr uint64_t TRACE_TAIL_PAD = 16;
+struct TraceLayout { uint64_t innerq_at, leaves_at, bytes, alloc_bytes; };
 inline TraceLayout trace_layout(uint64_t n_inner, uint64_t n_innerq, uint64_t n_leaves) {
   TraceLayout t;
   t.innerq_at = n_inner * sizeof(izd::GInner);
   t.leaves_at = t.innerq_at + n_innerq * sizeof(izd::GInnerQ);
   t.bytes = t.leaves_at + n_leaves * sizeof(izd::GLeaf);
+  t.alloc_bytes = t.bytes + TRACE_TAIL_PAD;
   return t;
 }
 // DevScene::addr32: every record of the node block starts below 4 GiB from the block's base, and

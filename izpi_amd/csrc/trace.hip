@@ -59,6 +59,16 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
   static_assert(!L3 || DIST, "the leaf size bound shapes the distributed primitive step");
   static_assert(!FT || L3, "the fixed tMin is compiled for the three-primitive leaf instances");
   constexpr uint32_t LEAF_MAX = L3 ? 3 : 4;  // entries a leaf can put into a batch
+  // SG: the global-memory instances that read the 128-B nodes load each axis's near and far plane
+  // by the ray's sign (slab_rule.h) and run slab4_sorted; the tree-in-LDS and the quantised ones
+  // load the planes in order and run slab4_fast. (So does the one-ray-per-lane sphere-capable
+  // instance on 64-bit addresses, IZPI_TUNE_NO_DIST on a scene past 4 GiB: six per-lane 64-bit
+  // addresses would spill 4 of its VGPRs to scratch.)
+  constexpr bool SG = !LB && !Q && (A32 || DIST || TRI);
+  // PK: the sphere-capable instances, which have no register to spare (96 of 96 for 5 waves per SIMD),
+  // carry the three near-plane indices as the bytes of one register and take them apart in the step.
+  constexpr bool PK = SG && !TRI;
+  typedef float v4fu __attribute__((ext_vector_type(4), aligned(4)));  // a leaf lane's 16-B loads start at any of its floats
   // (u, v) of the accepted hit: kept in lds_uv until the ray finishes (UVL), stored to the
   // hit record at acceptance (UVS: the BVH-in-LDS ray instance, whose steps issue no global
   // loads for the store to hold up), or not kept (C3's instance: nothing reads it)
@@ -145,7 +155,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
   int sp = -1, low = 0;
   int clean_from = 0;     // stack entries at positions >= clean_from were pushed after the last accepted hit
   int32_t bprim = -1;
-  bool fast = false;      // slab4_fast is exact for this ray
+  bool fast = false;      // slab4_fast / slab4_sorted is exact for this ray
+  // SG: which of the box's six bounds (GInner's order) is the near plane of each axis: renewed by
+  // each refill; 0, 1, 2 for a lane that is not fast
+  uint32_t nrx = 0, nry = 1, nrz = 2, nrp = 0x020100u;
   uint64_t m_slow = ~0ull;  // wave mask of !fast, renewed by each refill (wave-uniform)
   bool any_spill = false; // a lane of this wave has spilled ring entries (wave-uniform)
 #ifdef IZPI_SHADOW
@@ -240,6 +253,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
             ix = (float)(1.0 / r.d[0]); iy = (float)(1.0 / r.d[1]); iz = (float)(1.0 / r.d[2]);
             ox = (float)r.o[0]; oy = (float)r.o[1]; oz = (float)r.o[2];
             fast = sc.nan_free_bounds && ray_fast_ok(ox, oy, oz, ix, iy, iz);
+            if constexpr (SG) {
+              fast = fast && sc.ordered_bounds;
+              const uint32_t kx = slab_near_index(0, ix, fast), ky = slab_near_index(1, iy, fast), kz = slab_near_index(2, iz, fast);
+              if constexpr (PK) nrp = kx | (ky << 8) | (kz << 16);
+              else { nrx = kx; nry = ky; nrz = kz; }
+            }
             cur = sc.root;
             sp = cur != -1 ? 0 : -1; low = 0; clean_from = 0;
             bprim = -1;
@@ -492,13 +511,15 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
         const bool is_leaf = ref_is_leaf(cur);
         float4 q0, q1, mnz_, mxx_, mxy_, mxz_;
         int4 ch_;
+        float4 mnx, mny, mnz, mxx, mxy, mxz;  // SG: the near planes of x, y, z, then the far ones
         // the lane's record (lp: a leaf's GLeaf or the inner node) and the inner node's remaining
         // loads (np: leaf lanes read them from the root node, a cached valid address; the values
         // are not used)
         const float4 *lp = nullptr, *np = nullptr;
+        uint32_t loff = 0;  // A32: the record's offset in the node block
         if constexpr (!LB && A32) {
           const uint32_t noff = is_leaf ? 0u : (uint32_t)cur * NODE_BYTES;
-          const uint32_t loff = is_leaf ? leaf_off0 + (uint32_t)leaf_start(cur) * (uint32_t)sizeof(GLeaf) : noff;
+          loff = is_leaf ? leaf_off0 + (uint32_t)leaf_start(cur) * (uint32_t)sizeof(GLeaf) : noff;
           lp = reinterpret_cast<const float4*>(nbase + loff);
           np = reinterpret_cast<const float4*>(nbase + noff);
         } else if constexpr (!LB) {
@@ -537,8 +558,26 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
           mnz_ = dmnz; mxx_ = dmxx; mxy_ = dmxy; mxz_ = dmxz;
           ch_ = make_int4(__float_as_int(c2.z), __float_as_int(c2.w), __float_as_int(c3.x), __float_as_int(c3.y));
         } else {
-          q0 = lp[0]; q1 = lp[1];
-          mnz_ = np[2]; mxx_ = np[3]; mxy_ = np[4]; mxz_ = np[5];
+          if constexpr (SG) {
+            // Bound i of the record's box, for the node's four slots: an inner node's is the 16-B
+            // piece i of the record; a leaf's six floats are 4 B apart, and its bound arrives in
+            // component .x with no select (the load at mx[2] of the block's last leaf ends inside
+            // the block's tail pad, trace_layout). Slots 1-3 of a leaf lane hold what follows in
+            // memory: masked by m_inner below.
+            const uint32_t sh = is_leaf ? 2u : 4u;
+            if constexpr (PK) { nrx = nrp & 0xFFu; nry = (nrp >> 8) & 0xFFu; nrz = nrp >> 16; }
+            const uint32_t frx = slab_far_index(0, nrx), fry = slab_far_index(1, nry), frz = slab_far_index(2, nrz);
+            auto plane = [&](uint32_t i) {
+              const v4fu v = A32 ? *reinterpret_cast<const v4fu*>(nbase + (uint32_t)((i << sh) + loff))
+                                 : *reinterpret_cast<const v4fu*>(reinterpret_cast<const char*>(lp) + (i << sh));
+              return make_float4(v.x, v.y, v.z, v.w);
+            };
+            mnx = plane(nrx); mny = plane(nry); mnz = plane(nrz);
+            mxx = plane(frx); mxy = plane(fry); mxz = plane(frz);
+          } else {
+            q0 = lp[0]; q1 = lp[1];
+            mnz_ = np[2]; mxx_ = np[3]; mxy_ = np[4]; mxz_ = np[5];
+          }
           ch_ = *reinterpret_cast<const int4*>(np + 6);
 #ifdef IZPI_SHADOW
           if ((IZPI_SHADOW & 1) && !is_leaf) {
@@ -554,12 +593,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
 #endif
         }
         // GLeaf = (mn.x, mn.y, mn.z, mx.x), (mx.y, mx.z, start, count)
-        const float4 mnx = q0;
-        const float4 mny = make_float4(is_leaf ? q0.y : q1.x, q1.y, q1.z, q1.w);
-        const float4 mnz = make_float4(is_leaf ? q0.z : mnz_.x, mnz_.y, mnz_.z, mnz_.w);
-        const float4 mxx = make_float4(is_leaf ? q0.w : mxx_.x, mxx_.y, mxx_.z, mxx_.w);
-        const float4 mxy = make_float4(is_leaf ? q1.x : mxy_.x, mxy_.y, mxy_.z, mxy_.w);
-        const float4 mxz = make_float4(is_leaf ? q1.y : mxz_.x, mxz_.y, mxz_.z, mxz_.w);
+        if constexpr (!SG) {
+          mnx = q0;
+          mny = make_float4(is_leaf ? q0.y : q1.x, q1.y, q1.z, q1.w);
+          mnz = make_float4(is_leaf ? q0.z : mnz_.x, mnz_.y, mnz_.z, mnz_.w);
+          mxx = make_float4(is_leaf ? q0.w : mxx_.x, mxx_.y, mxx_.z, mxx_.w);
+          mxy = make_float4(is_leaf ? q1.x : mxy_.x, mxy_.y, mxy_.z, mxy_.w);
+          mxz = make_float4(is_leaf ? q1.y : mxz_.x, mxz_.y, mxz_.z, mxz_.w);
+        }
         const int4 ch = make_int4(is_leaf ? cur : ch_.x, ch_.y, ch_.z, ch_.w);
         // The four slot results are wave masks (one bit per lane, as the compares leave them),
         // combined on the scalar unit: a per-lane bit field costs the vector unit a select to
@@ -567,8 +608,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
         uint64_t hit[4];
         if (wave_fast) {
           IZPI_MARK("slab_fast");
-          slab4_fast(mnx, mny, mnz, mxx, mxy, mxz, ox, oy, oz, ix, iy, iz, tm, hit);
+          if constexpr (SG) slab4_sorted(mnx, mny, mnz, mxx, mxy, mxz, ox, oy, oz, ix, iy, iz, tm, hit);
+          else slab4_fast(mnx, mny, mnz, mxx, mxy, mxz, ox, oy, oz, ix, iy, iz, tm, hit);
         } else {
+          // (SG, a wave with fast and other lanes: a fast lane's planes come swapped on the axes it
+          // travels down; `slab`'s own swap is symmetric for its NaN-free values, so its result is
+          // the one for the planes in order)
           IZPI_MARK("slab_twin");
           const float amnx[4] = {mnx.x, mnx.y, mnx.z, mnx.w}, amny[4] = {mny.x, mny.y, mny.z, mny.w},
                       amnz[4] = {mnz.x, mnz.y, mnz.z, mnz.w}, amxx[4] = {mxx.x, mxx.y, mxx.z, mxx.w},
