@@ -330,6 +330,49 @@ int izpi_gpu_denoise_device(izpi_ctx* ctx, const double* colour_dev, const doubl
 int izpi_gpu_denoise(izpi_ctx* ctx, const double* colour, const double* normal, const double* albedo, double* out,
                      uint32_t width, uint32_t height, const izpi_denoise_params* p, double* device_ms);
 
+/* ---- Variance-guided denoising of a noise session's frame ----
+ * A second filter beside the one above, for frames that carry a measured error: the spatial
+ * filter of SVGF (Schied et al., HPG 2017, section 4.4) without its temporal part. It takes,
+ * with the canvas and the guides, the canvas of standard errors an IZPI_SNAP_NOISE snapshot
+ * writes (se_0, se_1, se_2, 1.0; the alpha is ignored), and measures every colour
+ * difference in the pixel's own variance, so that a pixel with many samples is left nearly
+ * alone and one with few is smoothed: what a progressive or an adaptive session (whose
+ * pixels carry different sample counts by design) needs. The project's own rule.
+ *
+ * V_0[p] = (se_0^2 + se_1^2) + se_2^2, a [H][W] float64 plane. A pixel is live when the
+ * filter above takes it (alpha != 0, finite colour) and its V is finite and >= 0; others
+ * are neither read as taps nor changed (their V is copied). Iteration i, taps `1 << i`
+ * apart, of a live pixel: g = V_i through a 3 x 3 kernel {1/4, 1/2, 1/4}^2 at unit spacing
+ * over the live pixels, kc = 1 / (sigma_colour^2 * (g + variance_floor)); then the 25 taps
+ * of the filter above with e = dc * kc + dn / sigma_normal^2 + da / sigma_albedo^2 and
+ * w = h * exp(-e); C_{i+1} = sum(w C_i) / sum(w), V_{i+1} = sum(w^2 V_i) / sum(w)^2.
+ * sigma_colour is not halved per iteration: the variance shrinks instead. iterations == 0
+ * copies the canvas and hands out V_0.
+ *
+ * p: an izpi_denoise_params under the rules above; p == NULL means 5 iterations, sigma_colour
+ * IZPI_DENOISE_VAR_DEFAULT_SIGMA_COLOUR, sigma_normal and sigma_albedo 0.5. variance_floor
+ * is finite and > 0 (IZPI_DENOISE_VAR_DEFAULT_FLOOR: the chosen default; it keeps a pixel
+ * whose samples happened to agree from freezing). stderr_dev is required; out may overlap
+ * neither an input nor var_out. var_out ([H][W] float64, may be NULL) receives the variance
+ * of the filtered canvas.
+ *
+ *  _denoise_var_device  all canvases and the plane in device memory. The colour ping-pong
+ *                       shares the scratch canvas of _denoise_device; two variance planes
+ *                       live in one more buffer of the context that only grows. Like
+ *                       _denoise_device it needs no scene, returns after the stream has
+ *                       finished and is allowed while a progressive session is open.
+ *  _denoise_var         the same over host memory.
+ *  izpi_host_denoise_var (izpi_host.h) is the twin on the host, bit for bit.
+ * Multi-GPU callers run it on izpi_gpu_multi_context(m, 0) over gathered snapshots. */
+#define IZPI_DENOISE_VAR_DEFAULT_SIGMA_COLOUR 1.5 /* and the floor: chosen on a grid, DESIGN 3.8a */
+#define IZPI_DENOISE_VAR_DEFAULT_FLOOR 1e-4
+int izpi_gpu_denoise_var_device(izpi_ctx* ctx, const double* colour_dev, const double* stderr_dev, const double* normal_dev,
+                                const double* albedo_dev, double* out_dev, double* var_out_dev, uint32_t width,
+                                uint32_t height, const izpi_denoise_params* p, double variance_floor, double* device_ms);
+int izpi_gpu_denoise_var(izpi_ctx* ctx, const double* colour, const double* stderr_host, const double* normal,
+                         const double* albedo, double* out, double* var_out, uint32_t width, uint32_t height,
+                         const izpi_denoise_params* p, double variance_floor, double* device_ms);
+
 /* GPU BVH4 builder: Morton codes and a radix sort, then a binary
  * tree (method: IZPI_BVH_PLOC clustering or IZPI_BVH_LBVH radix tree), collapsed to
  * 4-wide nodes with collectChildren's rule (or, with IZPI_BVH_SAH, the collapse of least

@@ -177,6 +177,15 @@ int izpi_host_displace(const izpi_tri_in* tris, uint64_t n, const double* rgba, 
 int izpi_host_denoise(const double* colour, const double* normal, const double* albedo, double* out, uint32_t width,
                       uint32_t height, const izpi_denoise_params* p);
 
+/* The host twin of izpi_gpu_denoise_var (izpi_gpu.h: the rule and the arguments are the same;
+ * the arithmetic is izpi_amd/csrc/denoise_var.h's), bit for bit what the device writes.
+ * stderr_host: the [H][W][4] canvas of standard errors (IZPI_SNAP_NOISE's form); var_out
+ * ([H][W], may be NULL): the variance of the filtered canvas. All pointers host; its error
+ * is izpi_host_last_error's. */
+int izpi_host_denoise_var(const double* colour, const double* stderr_host, const double* normal, const double* albedo,
+                          double* out, double* var_out, uint32_t width, uint32_t height, const izpi_denoise_params* p,
+                          double variance_floor);
+
 /* The host twin of izpi_gpu_progressive_noise and of the IZPI_SNAP_NOISE snapshot (izpi_gpu.h:
  * the rule is stated there; the arithmetic is izpi_amd/csrc/noise.h's, bit for bit what the
  * device gives): sums and moment2 are [num_pixels][3], the per-pixel sums and second moments

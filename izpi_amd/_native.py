@@ -44,6 +44,7 @@ DISPLACE_MAX_LEVELS = 16
 DENOISE_MAX_ITERATIONS = 8
 DENOISE_DEFAULT_ITERATIONS = 5
 DENOISE_DEFAULT_SIGMA_COLOUR, DENOISE_DEFAULT_SIGMA_NORMAL, DENOISE_DEFAULT_SIGMA_ALBEDO = 1.0, 0.5, 0.5
+DENOISE_VAR_DEFAULT_SIGMA_COLOUR, DENOISE_VAR_DEFAULT_FLOOR = 1.5, 1e-4  # the variance-guided filter's
 
 
 def prim_ref(kind, idx):
@@ -155,6 +156,12 @@ def denoise_params(iterations=DENOISE_DEFAULT_ITERATIONS, sigma_colour=DENOISE_D
                    sigma_normal=DENOISE_DEFAULT_SIGMA_NORMAL, sigma_albedo=DENOISE_DEFAULT_SIGMA_ALBEDO):
     """izpi_denoise_params; the defaults are the library's (what a NULL pointer means)."""
     return DenoiseParams(int(iterations), 0, float(sigma_colour), float(sigma_normal), float(sigma_albedo))
+
+
+def denoise_var_params(iterations=DENOISE_DEFAULT_ITERATIONS, sigma_colour=DENOISE_VAR_DEFAULT_SIGMA_COLOUR,
+                       sigma_normal=DENOISE_DEFAULT_SIGMA_NORMAL, sigma_albedo=DENOISE_DEFAULT_SIGMA_ALBEDO):
+    """izpi_denoise_params with the variance-guided filter's defaults (what its NULL pointer means)."""
+    return denoise_params(iterations, sigma_colour, sigma_normal, sigma_albedo)
 
 
 class NoiseParams(C.Structure):
@@ -278,6 +285,7 @@ EXPORTS = [
     "izpi_gpu_multi_progressive_begin_ex", "izpi_gpu_multi_progressive_noise", "izpi_gpu_multi_progressive_converge",
     "izpi_host_noise",
     "izpi_gpu_progressive_adapt", "izpi_gpu_multi_progressive_adapt", "izpi_host_adapt",
+    "izpi_gpu_denoise_var_device", "izpi_gpu_denoise_var", "izpi_host_denoise_var",
 ]
 
 _lib = None
@@ -394,6 +402,11 @@ def lib():
     denoise_args = [vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams)]  # colour, normal, albedo, out
     L.izpi_host_denoise.argtypes = denoise_args
     L.izpi_gpu_denoise.argtypes = [vp] + denoise_args + [c_double_p]
+    # colour, stderr, normal, albedo, out, var_out, width, height, params, variance_floor
+    denoise_var_args = [vp, vp, vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.POINTER(DenoiseParams), C.c_double]
+    L.izpi_host_denoise_var.argtypes = denoise_var_args
+    L.izpi_gpu_denoise_var.argtypes = [vp] + denoise_var_args + [c_double_p]
+    L.izpi_gpu_denoise_var_device.argtypes = [vp] + denoise_var_args + [c_double_p]
     # sums, moment2, counted, num_pixels, done, sampler, params, se_out, stats
     L.izpi_host_noise.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(NoiseParams), vp,
                                   C.POINTER(NoiseStats)]

@@ -1,0 +1,64 @@
+// denoise_var_host.cpp — izpi_host_denoise_var: the variance-guided a-trous denoiser on the
+// host, the plain sequential form of the arithmetic in denoise_var.h (DESIGN.md section
+// 3.8a). It is the twin the device path (denoise_var.hip) is tested against. No HIP here: a
+// host compiler builds it alone.
+#include <stdint.h>
+#include <string.h>
+
+#include <new>
+#include <string>
+#include <vector>
+
+#include "denoise_var.h"
+
+namespace izpi_internal {
+void set_host_error(const std::string& s);
+}
+
+namespace {
+
+template <bool HAS_N, bool HAS_A>
+void pass(const double* C, const double* V, const double* Nm, const double* A, int64_t W, int64_t H, const dnv::Iter& it,
+          double* out, double* vout) {
+  for (int64_t y = 0; y < H; y++)
+    for (int64_t x = 0; x < W; x++)
+      vout[y * W + x] = dnv::pixel<HAS_N, HAS_A>(C, V, Nm, A, W, H, x, y, it, out + (y * W + x) * 4);
+}
+
+}  // namespace
+
+extern "C" int izpi_host_denoise_var(const double* colour, const double* stderr_host, const double* normal,
+                                     const double* albedo, double* out, double* var_out, uint32_t width, uint32_t height,
+                                     const izpi_denoise_params* params, double variance_floor) {
+  const izpi_denoise_params p = params ? *params : dnv::defaults();
+  if (const char* bad = dnv::check_args(colour, stderr_host, normal, albedo, out, var_out, width, height, p, variance_floor)) {
+    izpi_internal::set_host_error(bad);
+    return IZPI_ERR_INVALID;
+  }
+  try {
+    const size_t pixels = (size_t)width * height, doubles = pixels * 4;
+    // two variance planes: iteration i reads plane i % 2 and writes the other
+    std::vector<double> planes[2] = {std::vector<double>(pixels), std::vector<double>(p.iterations ? pixels : 0)};
+    for (size_t q = 0; q < pixels; q++) planes[0][q] = dnv::variance0(stderr_host + q * 4);
+    if (p.iterations == 0) memcpy(out, colour, doubles * sizeof(double));
+    // ping-pong between `out` and one scratch canvas so that the last iteration lands in `out`
+    std::vector<double> scratch(p.iterations > 1 ? doubles : 0);
+    const double* src = colour;
+    for (uint32_t i = 0; i < p.iterations; i++) {
+      double* dst = (p.iterations - 1 - i) % 2 == 0 ? out : scratch.data();
+      const double* v = planes[i % 2].data();
+      double* vdst = planes[(i + 1) % 2].data();
+      const dnv::Iter it = dnv::iteration(p, variance_floor, i);
+      if (normal && albedo) pass<true, true>(src, v, normal, albedo, width, height, it, dst, vdst);
+      else if (normal) pass<true, false>(src, v, normal, albedo, width, height, it, dst, vdst);
+      else if (albedo) pass<false, true>(src, v, normal, albedo, width, height, it, dst, vdst);
+      else pass<false, false>(src, v, normal, albedo, width, height, it, dst, vdst);
+      src = dst;
+    }
+    if (var_out) memcpy(var_out, planes[p.iterations % 2].data(), pixels * sizeof(double));
+    return IZPI_OK;
+  } catch (const std::bad_alloc&) {
+    izpi_internal::set_host_error("out of host memory");
+    return IZPI_ERR_INVALID;
+  }
+}

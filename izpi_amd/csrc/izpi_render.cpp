@@ -10,7 +10,8 @@
 //               [--progressive STEP [--snapshots PREFIX]]
 //               [--denoise [N] [--denoise-sigma c,n,a]]
 //               [--progressive STEP --noise-threshold T [--noise-tolerated F] [--noise-floor L]
-//                [--min-samples K] [--noise-out se.pfm] [--adaptive [--samples-out n.pfm]]]
+//                [--min-samples K] [--noise-out se.pfm] [--adaptive [--samples-out n.pfm]]
+//                [--denoise-variance [N] [--denoise-sigma c,n,a] [--variance-floor F] [--variance-out v.pfm]]]
 //
 // --denoise [N] (--sampler colour or spectral) filters the frame with N iterations (default
 // IZPI_DENOISE_DEFAULT_ITERATIONS) of the edge-avoiding a-trous denoiser (izpi_gpu_denoise,
@@ -41,6 +42,18 @@
 // line instead, and the render ends when at most --noise-tolerated of the finite pixels are
 // still active. Every pixel of --out is that pixel of a render at its own sample count;
 // --samples-out gets the counts (IZPI_SNAP_SAMPLES) as a PFM.
+//
+// --denoise-variance [N] (with --progressive STEP --noise-threshold T, with or without --adaptive;
+// --sampler colour) filters the frame the session ends with by its own noise estimate, with N
+// iterations (default 5) of the variance-guided a-trous denoiser (izpi_gpu_denoise_var, DESIGN.md
+// section 3.8a): the Normal and Albedo guides (4 samples) are rendered before the session opens,
+// the IZPI_SNAP_CANVAS and IZPI_SNAP_NOISE snapshots are filtered on the device, and one
+//   IZPI_DENOISE_VAR iterations= sigma_colour= floor= ms=
+// line is printed. --out / --raw get the filtered canvas, --variance-out its variance plane as a
+// PFM (the value in all three channels). --denoise-sigma is this filter's too (defaults
+// IZPI_DENOISE_VAR_DEFAULT_SIGMA_COLOUR, 0.5, 0.5); --variance-floor defaults to
+// IZPI_DENOISE_VAR_DEFAULT_FLOOR. A Spectral frame is filtered in XYZ ahead of its
+// post-processing, which needs device canvases: through the library, not this tool.
 //
 // Defaults are the Go shim's: the GPU-built tree and the forward accumulation
 // (IZPI_ACC_FORWARD; --accumulation recursive is bit-identical to the CPU oracle).
@@ -111,6 +124,10 @@ int main(int argc, char** argv) {
   bool denoise = false;
   izpi_denoise_params dparams = {IZPI_DENOISE_DEFAULT_ITERATIONS, 0, IZPI_DENOISE_DEFAULT_SIGMA_COLOUR,
                                  IZPI_DENOISE_DEFAULT_SIGMA_NORMAL, IZPI_DENOISE_DEFAULT_SIGMA_ALBEDO};
+  bool dvar = false, sigma_given = false;
+  uint32_t dvar_iterations = IZPI_DENOISE_DEFAULT_ITERATIONS;
+  double variance_floor = IZPI_DENOISE_VAR_DEFAULT_FLOOR;
+  std::string variance_out;
   bool noise = false;
   izpi_noise_params nparams = {IZPI_NOISE_DEFAULT_THRESHOLD, IZPI_NOISE_DEFAULT_FLOOR, IZPI_NOISE_DEFAULT_TOLERATED,
                                IZPI_NOISE_DEFAULT_MIN_SPP, 0};
@@ -150,7 +167,14 @@ int main(int argc, char** argv) {
     else if (a == "--denoise-sigma") {
       if (sscanf(val().c_str(), "%lf,%lf,%lf", &dparams.sigma_colour, &dparams.sigma_normal, &dparams.sigma_albedo) != 3)
         die("--denoise-sigma takes colour,normal,albedo");
+      sigma_given = true;
     }
+    else if (a == "--denoise-variance") {
+      dvar = true;
+      if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') dvar_iterations = (uint32_t)atoi(argv[++i]);
+    }
+    else if (a == "--variance-floor") variance_floor = atof(val().c_str());
+    else if (a == "--variance-out") variance_out = val();
     else if (a == "--noise-threshold") { noise = true; nparams.threshold = atof(val().c_str()); }
     else if (a == "--noise-tolerated") nparams.tolerated = atof(val().c_str());
     else if (a == "--noise-floor") nparams.floor = atof(val().c_str());
@@ -169,6 +193,13 @@ int main(int argc, char** argv) {
   if (!noise_out.empty() && !noise) die("--noise-out needs --noise-threshold");
   if (adaptive && !noise) die("--adaptive needs --progressive and --noise-threshold");
   if (!samples_out.empty() && !adaptive) die("--samples-out needs --adaptive");
+  if (dvar && !noise) die("--denoise-variance needs --progressive and --noise-threshold");
+  if (dvar && denoise) die("--denoise-variance and --denoise are two filters: name one");
+  if (!variance_out.empty() && !dvar) die("--variance-out needs --denoise-variance");
+  if (dvar) {
+    dparams.iterations = dvar_iterations;
+    if (!sigma_given) dparams.sigma_colour = IZPI_DENOISE_VAR_DEFAULT_SIGMA_COLOUR;
+  }
   // ---- scene file (leader.go:54-75)
   std::vector<char> text;
   if (!read_file(scene_path, text)) die("cannot read " + scene_path);
@@ -216,6 +247,8 @@ int main(int argc, char** argv) {
   if (denoise && progressive) die("--denoise filters a whole frame: not with --progressive");
   if (denoise && png) die("--denoise filters linear values: not with --png-pipeline");
   if (adaptive && sampler != IZPI_SAMPLER_COLOUR && !spectral) die("--adaptive needs --sampler colour or spectral");
+  if (dvar && sampler != IZPI_SAMPLER_COLOUR) die("--denoise-variance needs --sampler colour");
+  if (dvar && png) die("--denoise-variance filters linear values: not with --png-pipeline");
   // ---- transport.ToScene, BVH, upload
   auto t0 = std::chrono::steady_clock::now();
   const izpi_scene_input* in = nullptr;
@@ -271,6 +304,23 @@ int main(int argc, char** argv) {
   uint32_t spent = spp;  // samples per pixel in the canvas (fewer when the noise rule stopped the render)
   uint64_t rendered = 0;  // --adaptive: the samples rendered, the sum of the pixels' own counts
   auto t1 = std::chrono::steady_clock::now();
+  // --denoise-variance: the guides share the frame's primary rays; renders are refused while a
+  // session is open, so they come first. dv_se: the standard errors of the frame the session ends with.
+  std::vector<double> dv_normal, dv_albedo, dv_se;
+  if (dvar) {
+    dv_normal.resize(canvas.size());
+    dv_albedo.resize(canvas.size());
+    std::vector<izpi_render_stats> gst(stv.size());
+    izpi_render_req g = req;
+    g.post = IZPI_POST_NONE;
+    g.spp = 4;
+    for (int k = 0; k < 2; k++) {
+      g.sampler = k ? IZPI_SAMPLER_ALBEDO : IZPI_SAMPLER_NORMAL;
+      double* into = k ? dv_albedo.data() : dv_normal.data();
+      if (multi ? izpi_gpu_multi_render(multi, &g, into, gst.data()) : izpi_gpu_render(ctx, &g, into, gst.data()))
+        die(multi ? izpi_gpu_multi_last_error(multi) : izpi_gpu_last_error(ctx));
+    }
+  }
   if (progressive) {
     // the frame in steps; a snapshot after each (the last one is the frame)
     auto ok = [&](int r) { if (r) die(multi ? izpi_gpu_multi_last_error(multi) : izpi_gpu_last_error(ctx)); };
@@ -305,6 +355,12 @@ int main(int argc, char** argv) {
                    : izpi_gpu_progressive_snapshot(ctx, IZPI_SNAP_NOISE, se.data()));
           write_pfm(noise_out, se, W, H);
         }
+        if (dvar) {
+          if (done < 2) die("--denoise-variance needs a frame of at least 2 samples");
+          dv_se.resize(canvas.size());
+          ok(multi ? izpi_gpu_multi_progressive_snapshot(multi, IZPI_SNAP_NOISE, dv_se.data())
+                   : izpi_gpu_progressive_snapshot(ctx, IZPI_SNAP_NOISE, dv_se.data()));
+        }
         if (!samples_out.empty()) {  // the sample-count map
           std::vector<double> map((size_t)W * H * 4);
           ok(multi ? izpi_gpu_multi_progressive_snapshot(multi, IZPI_SNAP_SAMPLES, map.data())
@@ -322,6 +378,21 @@ int main(int argc, char** argv) {
     if (izpi_gpu_multi_render(multi, &req, canvas.data(), stv.data())) die(izpi_gpu_multi_last_error(multi));
   } else if (izpi_gpu_render(ctx, &req, canvas.data(), stv.data())) {
     die(izpi_gpu_last_error(ctx));
+  }
+  if (dvar) {  // (after a multi-GPU gather: on device 0's context, over the gathered snapshots)
+    std::vector<double> filtered(canvas.size()), plane((size_t)W * H);
+    double ms = 0;
+    if (izpi_gpu_denoise_var(ctx, canvas.data(), dv_se.data(), dv_normal.data(), dv_albedo.data(), filtered.data(),
+                             plane.data(), W, H, &dparams, variance_floor, &ms))
+      die(izpi_gpu_last_error(ctx));
+    canvas.swap(filtered);
+    fprintf(stderr, "IZPI_DENOISE_VAR iterations=%u sigma_colour=%.6g floor=%.6g ms=%.3f\n", dparams.iterations,
+            dparams.sigma_colour, variance_floor, ms);
+    if (!variance_out.empty()) {
+      std::vector<double> v4(canvas.size());
+      for (size_t q = 0; q < plane.size(); q++) v4[4 * q] = v4[4 * q + 1] = v4[4 * q + 2] = plane[q];
+      write_pfm(variance_out, v4, W, H);
+    }
   }
   if (denoise) {
     // the guides share the frame's primary rays (same seed, same streams), then the filter

@@ -120,6 +120,67 @@ def denoise_device(ctx, colour_ptr, normal_ptr, albedo_ptr, out_ptr, width, heig
     return ms.value
 
 
+def _stderr_arg(colour, stderr):
+    stderr = np.ascontiguousarray(stderr, np.float64)
+    if stderr.shape != colour.shape:
+        raise ValueError("the standard errors have the colour canvas's shape")
+    return stderr
+
+
+def _floor(variance_floor):
+    return C.c_double(N.DENOISE_VAR_DEFAULT_FLOOR if variance_floor is None else float(variance_floor))
+
+
+def host_denoise_var(colour, stderr, normal=None, albedo=None, params=None, variance_floor=None):
+    """izpi_host_denoise_var: the variance-guided denoiser's host twin over
+    (H, W, 4) float64 canvases; stderr is the canvas of standard errors (N.SNAP_NOISE's form),
+    normal / albedo the guides or None, params an N.DenoiseParams (None = that filter's
+    defaults), variance_floor None = N.DENOISE_VAR_DEFAULT_FLOOR. Returns (canvas, variance
+    (H, W)). Needs no GPU."""
+    colour, normal, albedo = _canvas_args(colour, normal, albedo)
+    stderr = _stderr_arg(colour, stderr)
+    out = np.zeros_like(colour)
+    var = np.zeros(colour.shape[:2], np.float64)
+    L = N.lib()
+    rc = L.izpi_host_denoise_var(_ptr(colour), _ptr(stderr), _ptr(normal), _ptr(albedo), _ptr(out), _ptr(var),
+                                 colour.shape[1], colour.shape[0], None if params is None else C.byref(params),
+                                 _floor(variance_floor))
+    if rc != 0:
+        raise RuntimeError("izpi_host_denoise_var failed (status %d): %s" % (rc, L.izpi_host_last_error().decode()))
+    return out, var
+
+
+def denoise_var(ctx, colour, stderr, normal=None, albedo=None, params=None, variance_floor=None, timing=None):
+    """izpi_gpu_denoise_var on context `ctx` over host canvases (upload, filter, download):
+    host_denoise_var's arguments and results, bit for bit. timing (a dict) receives "ms"."""
+    colour, normal, albedo = _canvas_args(colour, normal, albedo)
+    stderr = _stderr_arg(colour, stderr)
+    out = np.zeros_like(colour)
+    var = np.zeros(colour.shape[:2], np.float64)
+    ms = C.c_double()
+    _check(N.lib().izpi_gpu_denoise_var(ctx, _ptr(colour), _ptr(stderr), _ptr(normal), _ptr(albedo), _ptr(out), _ptr(var),
+                                        colour.shape[1], colour.shape[0], None if params is None else C.byref(params),
+                                        _floor(variance_floor), C.byref(ms)),
+           ctx, "izpi_gpu_denoise_var")
+    if timing is not None:
+        timing["ms"] = ms.value
+    return out, var
+
+
+def denoise_var_device(ctx, colour_ptr, stderr_ptr, normal_ptr, albedo_ptr, out_ptr, var_out_ptr, width, height,
+                       params=None, variance_floor=None):
+    """izpi_gpu_denoise_var_device on context `ctx`: device pointers (normal_ptr, albedo_ptr and
+    var_out_ptr, the (H, W) plane, may be None); returns the device ms of the iterations."""
+    ms = C.c_double()
+    _check(N.lib().izpi_gpu_denoise_var_device(ctx, C.c_void_p(colour_ptr), C.c_void_p(stderr_ptr),
+                                               C.c_void_p(normal_ptr or 0), C.c_void_p(albedo_ptr or 0),
+                                               C.c_void_p(out_ptr), C.c_void_p(var_out_ptr or 0), width, height,
+                                               None if params is None else C.byref(params), _floor(variance_floor),
+                                               C.byref(ms)),
+           ctx, "izpi_gpu_denoise_var_device")
+    return ms.value
+
+
 def host_noise(sums, moment2, done, sampler=N.SAMPLER_COLOUR, counted=None, params=None):
     """izpi_host_noise: the host twin of a progressive session's noise estimate (DESIGN.md
     3.9) over (n, 3) float64 sums and second moments after `done` samples, in packed pixel
@@ -350,6 +411,45 @@ class ProgressiveSession:
         _check(N.lib().izpi_gpu_progressive_snapshot_device(self._handle, int(form), C.c_void_p(out_ptr)), self._handle,
                "izpi_gpu_progressive_snapshot_device")
 
+    def denoised(self, guides, params=None, variance_floor=None, post=N.POST_NONE):
+        """The frame after `done` >= 2 samples through the variance-guided filter (DESIGN.md
+        3.8a), of a single-GPU noise session begun with post=N.POST_NONE over the whole canvas:
+        the CANVAS and the NOISE snapshot into device canvases, izpi_gpu_denoise_var_device on
+        them with `guides` (GPURenderer.render_guides(), taken before the session was opened),
+        then for the Spectral sampler with N.POST_SPECTRAL in `post` izpi_gpu_spectral_post of
+        the filtered XYZ (the standard errors are XYZ's, so the filter runs on the sums' own
+        space, ahead of FireflyRejection), then N.POST_GAMMA_CLAMP's Gamma and Clamp. An
+        adaptive session needs nothing more: its snapshots already divide by the pixels' own
+        counts. Returns (canvas, variance): host arrays, the variance (H, W) that of the
+        filtered frame before `post`. The session's sums are not touched."""
+        import torch
+        if self._multi:
+            raise ValueError("a multi-GPU session gathers its snapshots; filter them on izpi_gpu_multi_context(m, 0)")
+        if self._req.out_layout != N.OUT_CANVAS or self._req.post != N.POST_NONE:
+            raise ValueError("denoised() needs a session over the canvas begun with post=N.POST_NONE")
+        r = self._owner
+        spectral = self._req.sampler == N.SAMPLER_SPECTRAL
+        if post & N.POST_SPECTRAL and not spectral:
+            raise ValueError("N.POST_SPECTRAL needs the Spectral sampler")
+        normal, albedo = guides
+        dev = torch.device("cuda", r.device)
+        shape = (self._req.height, self._req.width, 4)
+        colour, se, out = (torch.zeros(shape, dtype=torch.float64, device=dev) for _ in range(3))
+        var = torch.zeros(shape[:2], dtype=torch.float64, device=dev)
+        torch.cuda.synchronize(dev)  # the zero fills run on torch's stream, the library on its own
+        self.snapshot_device(colour.data_ptr(), N.SNAP_CANVAS)
+        self.snapshot_device(se.data_ptr(), N.SNAP_NOISE)
+        self.denoise_ms = denoise_var_device(self._handle, colour.data_ptr(), se.data_ptr(),
+                                             None if normal is None else normal.data_ptr(),
+                                             None if albedo is None else albedo.data_ptr(), out.data_ptr(),
+                                             var.data_ptr(), shape[1], shape[0], params, variance_floor)
+        if post & N.POST_SPECTRAL:
+            r.spectral_post(out.data_ptr(), colour.data_ptr())
+            out = colour
+        if post & N.POST_GAMMA_CLAMP:
+            r.postprocess(out.data_ptr(), [(N.FILTER_GAMMA, 0.0), (N.FILTER_CLAMP, 1.0)])
+        return out.cpu().numpy(), var.cpu().numpy()
+
     def close(self):
         if self._open and getattr(self._owner, "m" if self._multi else "ctx", None):
             self._open = False
@@ -538,6 +638,27 @@ class GPURenderer:
         normal_ptr / albedo_ptr may be None, params is an N.DenoiseParams (None = the library's
         defaults). Returns the device ms. Allowed while a progressive session is open."""
         return denoise_device(self.ctx, colour_ptr, normal_ptr, albedo_ptr, out_ptr, self.width, self.height, params)
+
+    def render_guides(self, aov_spp=4, albedo=None):
+        """The Normal frame and (albedo=True; the default for Colour, off for Spectral) the
+        Albedo frame of this view at `aov_spp` samples, as device canvases (torch tensors):
+        (normal, albedo or None), the guides of ProgressiveSession.denoised. Call it before the
+        session is opened: renders are refused while one is open."""
+        import torch
+        if albedo is None:
+            albedo = self.sampler != N.SAMPLER_SPECTRAL
+        dev = torch.device("cuda", self.device)
+        shape = (self.height, self.width, 4)
+        guides = [torch.zeros(shape, dtype=torch.float64, device=dev) for _ in range(2 if albedo else 1)]
+        torch.cuda.synchronize(dev)  # the zero fills run on torch's stream, the library on its own
+        own, stats = self.sampler, self.stats
+        try:
+            for canvas, sampler in zip(guides, (N.SAMPLER_NORMAL, N.SAMPLER_ALBEDO)):
+                self.sampler = sampler
+                self.render_device(canvas.data_ptr(), spp=aov_spp)
+        finally:
+            self.sampler, self.stats = own, stats  # (the frame's, not the guides')
+        return guides[0], guides[1] if albedo else None
 
     def render_denoised(self, spp=None, aov_spp=4, params=None, post=N.POST_NONE, albedo=None):
         """A denoised frame of this renderer's sampler (Colour, or Spectral through
