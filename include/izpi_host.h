@@ -178,7 +178,7 @@ int izpi_host_denoise(const double* colour, const double* normal, const double* 
                       uint32_t height, const izpi_denoise_params* p);
 
 /* The host twin of izpi_gpu_denoise_var (izpi_gpu.h: the rule and the arguments are the same;
- * the arithmetic is izpi_amd/csrc/denoise_var.h's), bit for bit what the device writes.
+ * the arithmetic is izpi_amd/csrc/denoise.h's), bit for bit what the device writes.
  * stderr_host: the [H][W][4] canvas of standard errors (IZPI_SNAP_NOISE's form); var_out
  * ([H][W], may be NULL): the variance of the filtered canvas. All pointers host; its error
  * is izpi_host_last_error's. */

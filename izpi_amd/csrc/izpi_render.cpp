@@ -304,22 +304,23 @@ int main(int argc, char** argv) {
   uint32_t spent = spp;  // samples per pixel in the canvas (fewer when the noise rule stopped the render)
   uint64_t rendered = 0;  // --adaptive: the samples rendered, the sum of the pixels' own counts
   auto t1 = std::chrono::steady_clock::now();
-  // --denoise-variance: the guides share the frame's primary rays; renders are refused while a
-  // session is open, so they come first. dv_se: the standard errors of the frame the session ends with.
-  std::vector<double> dv_normal, dv_albedo, dv_se;
-  if (dvar) {
-    dv_normal.resize(canvas.size());
-    dv_albedo.resize(canvas.size());
+  // The Normal or Albedo guide of a filter: it shares the frame's primary rays (same seed, same streams).
+  auto guide = [&](uint32_t which, std::vector<double>& into) {
     std::vector<izpi_render_stats> gst(stv.size());
     izpi_render_req g = req;
     g.post = IZPI_POST_NONE;
-    g.spp = 4;
-    for (int k = 0; k < 2; k++) {
-      g.sampler = k ? IZPI_SAMPLER_ALBEDO : IZPI_SAMPLER_NORMAL;
-      double* into = k ? dv_albedo.data() : dv_normal.data();
-      if (multi ? izpi_gpu_multi_render(multi, &g, into, gst.data()) : izpi_gpu_render(ctx, &g, into, gst.data()))
-        die(multi ? izpi_gpu_multi_last_error(multi) : izpi_gpu_last_error(ctx));
-    }
+    g.spp = 4;  // render_denoised's aov_spp
+    g.sampler = which;
+    into.resize(canvas.size());
+    if (multi ? izpi_gpu_multi_render(multi, &g, into.data(), gst.data()) : izpi_gpu_render(ctx, &g, into.data(), gst.data()))
+      die(multi ? izpi_gpu_multi_last_error(multi) : izpi_gpu_last_error(ctx));
+  };
+  // --denoise-variance: renders are refused while a session is open, so the guides come first.
+  // dv_se: the standard errors of the frame the session ends with.
+  std::vector<double> dv_normal, dv_albedo, dv_se;
+  if (dvar) {
+    guide(IZPI_SAMPLER_NORMAL, dv_normal);
+    guide(IZPI_SAMPLER_ALBEDO, dv_albedo);
   }
   if (progressive) {
     // the frame in steps; a snapshot after each (the last one is the frame)
@@ -395,17 +396,8 @@ int main(int argc, char** argv) {
     }
   }
   if (denoise) {
-    // the guides share the frame's primary rays (same seed, same streams), then the filter
-    std::vector<double> normal(canvas.size()), albedo(spectral ? 0 : canvas.size()), filtered(canvas.size());
-    std::vector<izpi_render_stats> gst(stv.size());
-    izpi_render_req g = req;
-    g.post = IZPI_POST_NONE;
-    g.spp = 4;  // render_denoised's aov_spp
-    auto guide = [&](uint32_t which, std::vector<double>& into) {
-      g.sampler = which;
-      if (multi ? izpi_gpu_multi_render(multi, &g, into.data(), gst.data()) : izpi_gpu_render(ctx, &g, into.data(), gst.data()))
-        die(multi ? izpi_gpu_multi_last_error(multi) : izpi_gpu_last_error(ctx));
-    };
+    // the guides, then the filter
+    std::vector<double> normal, albedo, filtered(canvas.size());
     guide(IZPI_SAMPLER_NORMAL, normal);
     if (!spectral) guide(IZPI_SAMPLER_ALBEDO, albedo);
     double ms = 0;

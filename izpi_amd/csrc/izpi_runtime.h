@@ -6,8 +6,8 @@
 //   session.hip     progressive sessions on one context, their noise estimate and stop rule;
 //   multi.hip       the share plan, device groups in one process (and their sessions), RCCL ranks;
 //   components.hip  post-processing and the component entries the tests call;
-//   trace.hip, wavefront.hip, preview.hip, resolve.hip, noise.hip, adapt.hip, denoise.hip,
-//   denoise_var.hip: the kernels a render or a filter runs, each with its launch code.
+//   trace.hip, wavefront.hip, preview.hip, resolve.hip, noise.hip, adapt.hip, denoise.hip:
+//   the kernels a render or a filter runs, each with its launch code.
 // The shade_*.hip units need none of this (izpi_kern.h). Not part of the ABI.
 #pragma once
 #include <atomic>
@@ -173,8 +173,8 @@ struct izpi_ctx {
   double* d_post = nullptr; size_t post_cap = 0;      // spectral post-processing output
   double* d_share = nullptr; size_t share_cap = 0;    // multi-GPU: this device's packed tiles
   double* d_gather = nullptr; size_t gather_cap = 0;  // multi-GPU root: every device's packed tiles
-  double* d_denoise = nullptr; size_t denoise_cap = 0;  // izpi_gpu_denoise_device's scratch canvas (denoise.hip; it only grows)
-  double* d_dnvar = nullptr; size_t dnvar_cap = 0;  // izpi_gpu_denoise_var_device's two variance planes (denoise_var.hip; it only grows)
+  double* d_denoise = nullptr; size_t denoise_cap = 0;  // the two denoisers' scratch canvas (denoise.hip; it only grows)
+  double* d_dnvar = nullptr; size_t dnvar_cap = 0;  // izpi_gpu_denoise_var_device's two variance planes (denoise.hip; it only grows)
   // a session begun with IZPI_PROG_NOISE (noise.hip; both only grow, and no workspace plan counts them):
   double* d_moments = nullptr; size_t moments_cap = 0;  // the samples' second moments, [num_pixels][3]
   double* d_noisepart = nullptr; size_t noisepart_cap = 0;  // k_noise_stats' block partials: [blocks] sums, then [blocks][4] counts

@@ -1,5 +1,5 @@
 // denoise_var_check.cpp — a stand-alone program over izpi_host_denoise_var (izpi_amd/csrc/
-// denoise_var_host.cpp; host_scene.cpp and scene_pack.cpp hold the host error string), built
+// denoise_host.cpp; host_scene.cpp and scene_pack.cpp hold the host error string), built
 // by tests/test_denoise_var.py with -fsanitize=address,undefined: every canvas and plane is a
 // heap block of exactly its size, so a tap or a store one pixel outside the image ends the
 // program. It runs the sizes of the parity cases with every guide set and iteration count,

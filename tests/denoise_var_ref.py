@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE — the variance-guided a-trous denoiser restated
-in plain Python, independent of izpi_amd/csrc/denoise_var.h: float loops in the stated order
+in plain Python, independent of izpi_amd/csrc/denoise.h: float loops in the stated order
 (Python floats are IEEE doubles and nothing here contracts to an FMA), with exp through
 izpi_host_gomath (gomath.h's exp, op 3), as tests/denoise_ref.py does for the filter of
 section 3.8. Also the seeded standard errors and the cases the filter's tests share."""

@@ -1,5 +1,5 @@
 """The variance-guided a-trous denoiser without a GPU: the host twin
-(izpi_host_denoise_var, izpi_amd/csrc/denoise_var_host.cpp) against the Python restatement
+(izpi_host_denoise_var, izpi_amd/csrc/denoise_host.cpp) against the Python restatement
 (tests/denoise_var_ref.py) to the byte, canvas and variance plane; hand cases that follow from
 the rule; the argument checks; the entries' declarations; a stand-alone program under
 AddressSanitizer and UBSan; and the measurement the filter exists for: on a Cornell box it
@@ -263,7 +263,7 @@ def test_stand_alone_program_is_clean_under_asan_and_ubsan(tmp_path):
     exe = tmp_path / "denoise_var_check"
     subprocess.run(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-fsanitize=address,undefined",
                     "-fno-sanitize-recover=all", "-o", str(exe), str(ROOT / "tests" / "denoise_var_check.cpp"),
-                    str(CSRC / "denoise_var_host.cpp"), str(CSRC / "host_scene.cpp"), str(CSRC / "scene_pack.cpp")], check=True)
+                    str(CSRC / "denoise_host.cpp"), str(CSRC / "host_scene.cpp"), str(CSRC / "scene_pack.cpp")], check=True)
     run = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
     assert run.returncode == 0, (run.stdout[-2000:], run.stderr[-3000:])  # a sanitizer report ends the program
     lines = run.stdout.splitlines()

@@ -1,5 +1,5 @@
 """The variance-guided a-trous denoiser on the GPU (izpi_gpu_denoise_var, izpi_gpu_denoise_var_device,
-izpi_amd/csrc/denoise_var.hip): to the byte against the host twin
+izpi_amd/csrc/denoise.hip): to the byte against the host twin
 (izpi_host_denoise_var), which tests/test_denoise_var.py ties to the Python restatement without
 a GPU; the context's scratch shared with the filter of section 3.8; ProgressiveSession.denoised
 on a plain, an adaptive and a Spectral noise session against the twin applied to the numpy
@@ -113,6 +113,34 @@ def test_device_entry_equals_the_twin_on_many_blocks(ctx, gpu):
     denoise_var_device(ctx, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(), out.data_ptr(), None,
                        width, height, N.denoise_var_params(iterations=iterations))
     assert_same(out.cpu().numpy(), want)
+
+
+def test_device_entry_without_a_variance_output_equals_the_twin(ctx, gpu):
+    """The variance ping-pong's last write: with var_out_ptr=None it lands in a scratch plane,
+    with a plane in the caller's. 37 x 19 plain frames, both guides; iterations 0 (a copy),
+    1 (no scratch canvas), 2 and 5; then 2 again with a plane."""
+    import torch
+    width, height = 37, 19
+    dev = torch.device("cuda", gpu)
+    frames = VR.seeded(width, height)
+    d = [torch.from_numpy(f).to(dev) for f in frames]
+    out = torch.zeros((height, width, 4), dtype=torch.float64, device=dev)
+    var = torch.zeros((height, width), dtype=torch.float64, device=dev)
+    ptrs = [t.data_ptr() for t in d]
+    for iterations in (0, 1, 2, 5):
+        p = N.denoise_var_params(iterations=iterations)
+        out.fill_(7.0)
+        torch.cuda.synchronize(dev)
+        denoise_var_device(ctx, *ptrs, out.data_ptr(), None, width, height, p)
+        assert_same(out.cpu().numpy(), host_denoise_var(*frames, p)[0])
+    p = N.denoise_var_params(iterations=2)
+    out.fill_(7.0)
+    var.fill_(7.0)
+    torch.cuda.synchronize(dev)
+    denoise_var_device(ctx, *ptrs, out.data_ptr(), var.data_ptr(), width, height, p)
+    want, want_var = host_denoise_var(*frames, p)
+    assert_same(out.cpu().numpy(), want)
+    assert_same(var.cpu().numpy(), want_var)
 
 
 def test_argument_checks_match_the_twin(ctx):
