@@ -132,7 +132,14 @@ class RenderReq(C.Structure):
                 ("ink", C.c_double * 3)]
 
 
-class RenderStats(C.Structure):
+class _Stats(C.Structure):
+    """What the library reports back: a structure that reads as a dict of its fields (`pad` left out)."""
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
+
+
+class RenderStats(_Stats):
     _fields_ = [("rays", C.c_uint64), ("node_visits", C.c_uint64), ("tri_tests", C.c_uint64),
                 ("sph_tests", C.c_uint64), ("light_tri_tests", C.c_uint64), ("light_sph_tests", C.c_uint64),
                 ("samples", C.c_uint64), ("kernel_ms", C.c_double), ("shade_ms", C.c_double),
@@ -142,9 +149,6 @@ class RenderStats(C.Structure):
                 ("tail_sph_tests", C.c_uint64), ("parks", C.c_uint64), ("workspace_bytes", C.c_uint64),
                 ("scene_bytes", C.c_uint64), ("slots", C.c_uint32), ("rec_dense", C.c_uint32),
                 ("pool_blocks", C.c_uint32), ("chunk_spp", C.c_uint32), ("alloc_ms", C.c_double)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
 
 
 class DenoiseParams(C.Structure):
@@ -175,21 +179,15 @@ def noise_params(threshold=NOISE_DEFAULT_THRESHOLD, floor=NOISE_DEFAULT_FLOOR, t
     return NoiseParams(float(threshold), float(floor), float(tolerated), int(min_spp), 0)
 
 
-class NoiseStats(C.Structure):
+class NoiseStats(_Stats):
     _fields_ = [("pixels", C.c_uint64), ("nonfinite", C.c_uint64), ("above", C.c_uint64),
                 ("max_error", C.c_double), ("sum_error", C.c_double), ("device_ms", C.c_double),
                 ("done", C.c_uint32), ("converged", C.c_uint32)]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class AdaptStats(C.Structure):
+class AdaptStats(_Stats):
     _fields_ = [("pixels", C.c_uint64), ("nonfinite", C.c_uint64), ("active", C.c_uint64), ("retired", C.c_uint64),
                 ("samples", C.c_uint64), ("device_ms", C.c_double), ("done", C.c_uint32), ("converged", C.c_uint32)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class Hit(C.Structure):

@@ -36,3 +36,23 @@ def test_colour_preview_session_colour_on_one_context(gpu):
         assert s.snapshot().tobytes() == first.tobytes()
     colour_again()
     r.close()
+
+
+def test_use_tree_loads_what_a_fresh_renderer_loads(gpu):
+    """use_tree goes through the constructor's scene loader: after each of its three branches
+    (the GPU-built tree, the quantised upload, back to the reference tree) the context renders
+    the frame, counts the work and names the tree like a renderer opened with those arguments."""
+    scene = configs.cornell_dragon(1.0, n=24)
+    r = GPURenderer(scene, 32, 32, 2, bvh="reference")
+    r.render()
+    for tree in (dict(bvh="gpu"), dict(bvh="gpu", bvh_quantized=True), dict(bvh="reference")):
+        r.use_tree(scene, **tree)
+        img = r.render()
+        fresh = GPURenderer(scene, 32, 32, 2, **tree)
+        assert img.tobytes() == fresh.render().tobytes(), tree
+        for k in ("rays", "node_visits", "tri_tests", "light_tri_tests"):
+            assert r.stats[k] == fresh.stats[k], (tree, k)
+        assert (r.bvh_leaf_max, r.bvh_quantized) == (fresh.bvh_leaf_max, fresh.bvh_quantized), tree
+        assert (r.bvh_build_ms is None) == (fresh.bvh_build_ms is None) == (tree["bvh"] == "reference"), tree
+        fresh.close()
+    r.close()
