@@ -625,6 +625,60 @@ typedef struct izpi_adapt_stats {
 int izpi_gpu_progressive_adapt(izpi_ctx* ctx, const izpi_noise_params* p, izpi_adapt_stats* out);
 int izpi_gpu_multi_progressive_adapt(izpi_multi* m, const izpi_noise_params* p, izpi_adapt_stats* out);
 
+/* ---- Checkpoint and resume of a progressive session (deviation A28) ----
+ * A session's state lives in device memory of one process. A checkpoint is that state as one
+ * self-describing byte blob in host memory, which the caller stores wherever they like. Sample
+ * s of pixel (x, y) draws from its own stream, sums and moments fold in sample order, and a
+ * session's result depends neither on how its steps were cut nor on the share plan, so: A SESSION
+ * THAT IS EXPORTED, ENDED AND RESUMED IS, BIT FOR BIT, THE UNINTERRUPTED SESSION, in another
+ * process, on another context or over another number of devices: canvas, standard errors,
+ * sample-count map, adapt's integers and the reference counters. The project's own addition.
+ *
+ * The blob, little-endian: a 432-byte header, then per-pixel planes of width * height entries in
+ * sample-coordinate row-major order (y * W + x: sample rows, not canvas rows; no tile list and
+ * no share plan shows in it): a state byte (0 active, 1 retired, 2 retired as a counted
+ * non-finite pixel, 255 not in this session), the sums (3 doubles), with IZPI_PROG_NOISE the
+ * second moments (3 doubles), with IZPI_PROG_ADAPTIVE n_p (uint32); the byte and the uint32
+ * planes are padded to 8 bytes. A pixel that is not in the session holds zeros. The header
+ * (izpi_host_checkpoint_field reads it): magic "IZPICKPT", version, its size, the blob's size,
+ * a checksum of everything after it (FNV-1a over 64-bit words), the session flags and whether a
+ * pixel has retired, the request fields that decide a sample (width, height, sampler,
+ * accumulation, max_depth, seed, background, ink, the background SPD's length and digest), the
+ * session's distinct pixels, the caller's 64-bit scene tag (izpi_host_scene_tag), done, the sum
+ * of n_p, the active pixels, the cap at export, and the device counters: the six reference
+ * counters (rays, node_visits, tri_tests, sph_tests, light_tri_tests, light_sph_tests) with their
+ * values, the diagnostic ones (node_steps, prim_steps, leaf_shortcuts, the tail's share, parks)
+ * as 0: those depend on how the hardware scheduled the waves, differ between two runs of one
+ * session, and count from the resume on. No time and no pointer: the blob is a function of the
+ * session's state alone, and two exports of one state give the same bytes.
+ *
+ *  checkpoint_bytes  the blob's size for the open session.
+ *  checkpoint        writes the blob into out_host (cap bytes). Legal on an open session that is
+ *                    not broken and has done >= 1; the session stays as it was.
+ *  resume            _begin_ex's checks, plan and allocation with the flags taken from the blob,
+ *                    then the state, the integers and the counters are installed: progress and
+ *                    counters run on from the stored values, the times start at zero, and a
+ *                    further checkpoint gives the same bytes. These may differ from the exporting
+ *                    session's: spp (the new cap, >= done), step_spp, out_layout, post, exposure,
+ *                    tuning, and the tile list's order and shape; the SET of pixels must be equal.
+ * Refused with IZPI_ERR_INVALID and a message naming what failed, no session left open and the
+ * context usable: a short or truncated blob, a bad magic or version, a checksum mismatch, a
+ * deciding field that differs, the scene tag, spp < done, a session pixel without a record or a
+ * record no session pixel claims, a session already open, cap too small, a broken session,
+ * done == 0.
+ * The multi forms: a group exports one blob for the frame, byte for byte the one a single
+ * context exports at that state (the counters and the integers are the devices' sums); on resume
+ * every device installs the pixels of its own share and the first device with a share takes the
+ * stored counters, so that the devices' sums run on. */
+int izpi_gpu_progressive_checkpoint_bytes(izpi_ctx* ctx, uint64_t* bytes);
+int izpi_gpu_progressive_checkpoint(izpi_ctx* ctx, uint64_t scene_tag, void* out_host, uint64_t cap);
+int izpi_gpu_progressive_resume(izpi_ctx* ctx, const izpi_render_req* req, uint32_t step_spp, uint64_t scene_tag,
+                                const void* blob, uint64_t bytes);
+int izpi_gpu_multi_progressive_checkpoint_bytes(izpi_multi* m, uint64_t* bytes);
+int izpi_gpu_multi_progressive_checkpoint(izpi_multi* m, uint64_t scene_tag, void* out_host, uint64_t cap);
+int izpi_gpu_multi_progressive_resume(izpi_multi* m, const izpi_render_req* req, uint32_t step_spp, uint64_t scene_tag,
+                                      const void* blob, uint64_t bytes);
+
 /* Bytes of device output izpi_gpu_render_device writes for `req`. */
 uint64_t izpi_gpu_output_bytes(const izpi_render_req* req);
 

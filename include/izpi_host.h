@@ -209,6 +209,50 @@ int izpi_host_adapt(const double* sums, const double* moment2, const uint8_t* co
                     uint8_t* active, uint32_t num_pixels, uint32_t done, uint32_t sampler, const izpi_noise_params* p,
                     double* e_out, izpi_adapt_stats* stats);
 
+/* ======================================================================
+ * The checkpoint of a progressive session on the host (izpi_gpu.h states the format and the
+ * rule). None of these needs a GPU; their error is
+ * izpi_host_last_error's.
+ *
+ *  _field   one scalar of a blob's header (IZPI_CKPT_*; the doubles as their bits, counter k
+ *           as IZPI_CKPT_COUNTER + k, the planes' offsets from the blob's start, 0 for a plane
+ *           the session lacks). Checks the header only: a truncated blob still tells its size.
+ *  _check   the validation izpi_gpu_progressive_resume runs before it touches the device: the
+ *           blob is whole (size, magic, version, checksum), holds a sample, every deciding
+ *           field of `req` and the scene tag equal its own, and req->spp >= done.
+ *  _pack    k_ckpt_gather's twin: a session's state in the packed order of `tiles` (sums and
+ *           moment2 [num_pixels][3], samples and state [num_pixels]; moment2 is read with
+ *           IZPI_PROG_NOISE; samples and state come together and may be NULL: every pixel
+ *           active with `done` samples) into the frame-order planes, the blob's bytes after
+ *           its header. A pixel of no tile: state 255, zeros. *bytes (may be NULL) receives
+ *           their size; planes == NULL asks for that alone.
+ *  _unpack  k_ckpt_scatter's twin: the planes into the packed order of `tiles` (the outputs a
+ *           session with `flags` has are required). *absent: the pixels of `tiles` without a
+ *           record, which are left untouched; *unclaimed: the records no pixel took.
+ *  izpi_host_scene_tag  a 64-bit digest (the blob's word-wise FNV-1a) over every array of the
+ *           descriptor, its counts and flags, and the camera: what a caller passes as the
+ *           checkpoint's scene tag. The library hashes nothing at upload.
+ * ====================================================================== */
+enum {
+  IZPI_CKPT_VERSION = 0, IZPI_CKPT_HEADER_BYTES, IZPI_CKPT_BLOB_BYTES, IZPI_CKPT_CHECKSUM, IZPI_CKPT_FLAGS,
+  IZPI_CKPT_LISTED, IZPI_CKPT_WIDTH, IZPI_CKPT_HEIGHT, IZPI_CKPT_SAMPLER, IZPI_CKPT_ACCUMULATION, IZPI_CKPT_MAX_DEPTH,
+  IZPI_CKPT_NUM_BG_SPD, IZPI_CKPT_SEED, IZPI_CKPT_BG_DIGEST, IZPI_CKPT_PIXELS, IZPI_CKPT_SCENE_TAG, IZPI_CKPT_DONE,
+  IZPI_CKPT_SPP, IZPI_CKPT_SAMPLES, IZPI_CKPT_ACTIVE, IZPI_CKPT_NUM_COUNTERS, IZPI_CKPT_STATE_OFFSET,
+  IZPI_CKPT_SUMS_OFFSET, IZPI_CKPT_MOMENTS_OFFSET, IZPI_CKPT_COUNTS_OFFSET,
+  IZPI_CKPT_BACKGROUND = 32, /* + 0..2 */
+  IZPI_CKPT_INK = 36,        /* + 0..2 */
+  IZPI_CKPT_COUNTER = 64     /* + k, k < IZPI_CKPT_NUM_COUNTERS */
+};
+int izpi_host_checkpoint_field(const void* blob, uint64_t bytes, uint32_t which, uint64_t* out);
+int izpi_host_checkpoint_check(const void* blob, uint64_t bytes, const izpi_render_req* req, uint64_t scene_tag);
+int izpi_host_checkpoint_pack(uint32_t width, uint32_t height, const uint32_t* tiles, uint32_t num_tiles, uint32_t flags,
+                              uint32_t done, const double* sums, const double* moment2, const uint32_t* samples,
+                              const uint8_t* state, void* planes, uint64_t cap, uint64_t* bytes);
+int izpi_host_checkpoint_unpack(uint32_t width, uint32_t height, const uint32_t* tiles, uint32_t num_tiles, uint32_t flags,
+                                const void* planes, uint64_t bytes, double* sums, double* moment2, uint32_t* samples,
+                                uint8_t* state, uint64_t* absent, uint64_t* unclaimed);
+int izpi_host_scene_tag(const izpi_scene_desc* desc, uint64_t* out);
+
 /* sizeof() of the boundary structs: 0 izpi_bvh4_node 1 izpi_texture 2 izpi_material
  * 3 izpi_camera 4 izpi_scene_desc 5 izpi_render_req 6 izpi_render_stats 7 izpi_hit
  * 8 izpi_tri_in 9 izpi_sphere_in 10 izpi_camera_in 11 izpi_scene_input 12 izpi_proto_info

@@ -5,6 +5,7 @@ C++ host scene producer of include/izpi_host.h), and this thin Python host mirro
 (scene description, GPURenderer = render.Renderer drop-in, multi-GPU sharding).
 """
 from . import _native  # noqa: F401
+from .checkpoint import checkpoint_info  # noqa: F401  (a session's checkpoint as a dict; needs no GPU)
 
 # sampler.go:22-28 (samplerMap): the names izpi's --sampler takes and render.New's SamplerType
 # values, which are the IZPI_SAMPLER_* of include/izpi_gpu.h
@@ -12,4 +13,4 @@ SAMPLERS = {"colour": _native.SAMPLER_COLOUR, "normal": _native.SAMPLER_NORMAL,
             "wireframe": _native.SAMPLER_WIREFRAME, "albedo": _native.SAMPLER_ALBEDO,
             "spectral": _native.SAMPLER_SPECTRAL}
 
-__all__ = ["_native", "scene", "configs", "renderer", "build", "SAMPLERS"]
+__all__ = ["_native", "scene", "configs", "renderer", "build", "checkpoint", "checkpoint_info", "SAMPLERS"]

@@ -33,6 +33,11 @@ PROG_ADAPTIVE = 4  # ... with PROG_NOISE: stop sampling the pixels an adapt() fi
 SNAP_SAMPLES = 3  # an adaptive session's sample-count map
 # placeholders from one look at a 40 x 40 Cornell box (include/izpi_gpu.h says why min_spp exists)
 NOISE_DEFAULT_THRESHOLD, NOISE_DEFAULT_FLOOR, NOISE_DEFAULT_TOLERATED, NOISE_DEFAULT_MIN_SPP = 0.25, 0.01, 0.05, 8
+# izpi_host_checkpoint_field's scalars (include/izpi_host.h: IZPI_CKPT_*), in the enum's order
+CKPT_FIELDS = ("version", "header_bytes", "blob_bytes", "checksum", "flags", "listed", "width", "height", "sampler",
+               "accumulation", "max_depth", "num_bg_spd", "seed", "bg_digest", "pixels", "scene_tag", "done", "spp",
+               "samples", "active", "num_counters", "state_offset", "sums_offset", "moments_offset", "counts_offset")
+CKPT_BACKGROUND, CKPT_INK, CKPT_COUNTER = 32, 36, 64
 FILTER_GAMMA, FILTER_CLAMP = 1, 2
 MAX_FILTERS = 8
 HOST_SKIP_BVH = 1
@@ -284,6 +289,11 @@ EXPORTS = [
     "izpi_host_noise",
     "izpi_gpu_progressive_adapt", "izpi_gpu_multi_progressive_adapt", "izpi_host_adapt",
     "izpi_gpu_denoise_var_device", "izpi_gpu_denoise_var", "izpi_host_denoise_var",
+    "izpi_gpu_progressive_checkpoint_bytes", "izpi_gpu_progressive_checkpoint", "izpi_gpu_progressive_resume",
+    "izpi_gpu_multi_progressive_checkpoint_bytes", "izpi_gpu_multi_progressive_checkpoint",
+    "izpi_gpu_multi_progressive_resume",
+    "izpi_host_checkpoint_field", "izpi_host_checkpoint_check", "izpi_host_checkpoint_pack",
+    "izpi_host_checkpoint_unpack", "izpi_host_scene_tag",
 ]
 
 _lib = None
@@ -349,6 +359,22 @@ def lib():
         getattr(L, pre + "adapt").argtypes = [C.c_void_p, C.POINTER(NoiseParams), C.POINTER(AdaptStats)]
         getattr(L, pre + "converge").argtypes = [C.c_void_p, C.POINTER(NoiseParams), C.POINTER(RenderStats),
                                                  C.POINTER(NoiseStats)]
+        # a session's checkpoint: (bytes), (scene_tag, out_host, cap), (req, step_spp, scene_tag, blob, bytes)
+        getattr(L, pre + "checkpoint_bytes").argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        getattr(L, pre + "checkpoint").argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]
+        getattr(L, pre + "resume").argtypes = [C.c_void_p, C.POINTER(RenderReq), C.c_uint32, C.c_uint64, C.c_void_p,
+                                               C.c_uint64]
+    L.izpi_host_checkpoint_field.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]
+    L.izpi_host_checkpoint_check.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(RenderReq), C.c_uint64]
+    # width, height, tiles, num_tiles, flags, done, sums, moment2, samples, state, planes, cap, bytes
+    L.izpi_host_checkpoint_pack.argtypes = [C.c_uint32, C.c_uint32, c_uint32_p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                            C.POINTER(C.c_uint64)]
+    # width, height, tiles, num_tiles, flags, planes, bytes, sums, moment2, samples, state, absent, unclaimed
+    L.izpi_host_checkpoint_unpack.argtypes = [C.c_uint32, C.c_uint32, c_uint32_p, C.c_uint32, C.c_uint32, C.c_void_p,
+                                              C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.izpi_host_scene_tag.argtypes = [C.POINTER(SceneDesc), C.POINTER(C.c_uint64)]
     L.izpi_gpu_progressive_snapshot_device.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
     L.izpi_host_build_scene_ex.argtypes = [C.POINTER(SceneInput), C.c_uint32, C.POINTER(C.c_void_p)]
     L.izpi_host_scene_prim_boxes.argtypes = [C.c_void_p, c_double_p]

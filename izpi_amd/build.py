@@ -24,8 +24,9 @@ COMMON_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-ma
 SOURCES = [CSRC / "trace.hip", CSRC / "shade_colour.hip", CSRC / "shade_colour_fwd.hip", CSRC / "shade_spectral.hip",
            CSRC / "shade_spectral_fwd.hip", CSRC / "wavefront.hip", CSRC / "preview.hip", CSRC / "resolve.hip", CSRC / "izpi_gpu.hip", CSRC / "session.hip", CSRC / "multi.hip", CSRC / "components.hip", CSRC / "bvh_build.hip", CSRC / "host_scene.cpp",
            CSRC / "scene_pack.cpp", CSRC / "render_plan.cpp", CSRC / "scene_io.cpp", CSRC / "displace.hip", CSRC / "displace_host.cpp",
-           CSRC / "denoise.hip", CSRC / "denoise_host.cpp", CSRC / "noise.hip", CSRC / "noise_host.cpp", CSRC / "adapt.hip"]
-DEPS = SOURCES + [CSRC / "denoise.h", CSRC / "noise.h", CSRC / "pixel_map.h", CSRC / "displace.h", CSRC / "izpi_kern.h", CSRC / "izpi_runtime.h", CSRC / "shade.h", CSRC / "izpi_dev.h", CSRC / "scene_records.h", CSRC / "scene_pack.h", CSRC / "render_plan.h", CSRC / "izpi_req.h", CSRC / "gomath.h", CSRC / "cie_tables.h", CSRC / "lightsources.h",
+           CSRC / "denoise.hip", CSRC / "denoise_host.cpp", CSRC / "noise.hip", CSRC / "noise_host.cpp", CSRC / "adapt.hip",
+           CSRC / "checkpoint.hip", CSRC / "checkpoint_host.cpp"]
+DEPS = SOURCES + [CSRC / "denoise.h", CSRC / "noise.h", CSRC / "pixel_map.h", CSRC / "checkpoint.h", CSRC / "displace.h", CSRC / "izpi_kern.h", CSRC / "izpi_runtime.h", CSRC / "shade.h", CSRC / "izpi_dev.h", CSRC / "scene_records.h", CSRC / "scene_pack.h", CSRC / "render_plan.h", CSRC / "izpi_req.h", CSRC / "gomath.h", CSRC / "cie_tables.h", CSRC / "lightsources.h",
                   ROOT / "include" / "izpi_gpu.h", ROOT / "include" / "izpi_host.h", ROOT / "include" / "izpi_types.h", ROOT / "include" / "izpi_gpu_debug.h"]
 
 

@@ -116,6 +116,43 @@ __global__ void __launch_bounds__(BLOCK) k_adapt_scatter(const AdaptParams a) {
   *reinterpret_cast<uint4*>(a.table + 4 * (size_t)pos) = make_uint4(x, y, p, 0u);
 }
 
+// k_adapt_select for a session resumed from a checkpoint: the state bytes
+// are the stored ones, and no rule is evaluated (retirement is final, and the thresholds of the
+// earlier calls are not stored). It writes no state and no count; the blocks' three figures are
+// k_adapt_select's, so k_adapt_scan and k_adapt_scatter build the list an adapt would have left.
+__global__ void __launch_bounds__(BLOCK) k_adapt_select_state(const AdaptParams a) {
+  __shared__ uint32_t part[WAVES][3];
+  const uint32_t t = threadIdx.x;
+  const uint32_t p = blockIdx.x * BLOCK + t;
+  bool keep = false, counted = false, bad = false;
+  if (p < a.view.map.num_pixels) {
+    uint32_t x, y;
+    a.view.map.xy(p, &x, &y);
+    counted = y >= 1;
+    const uint8_t s = a.state[p];
+    keep = s == 0;
+    bad = s == 2;
+  }
+  const uint32_t n_keep = __popcll(__ballot(keep)), n_counted = __popcll(__ballot(counted)), n_bad = __popcll(__ballot(bad));
+  if ((t & 63u) == 0) {
+    uint32_t* w = part[t >> 6];
+    w[0] = n_keep; w[1] = n_counted; w[2] = n_bad;
+  }
+  __syncthreads();
+  if (t < 3) {
+    uint32_t v = part[0][t];
+    for (uint32_t w = 1; w < WAVES; w++) v += part[w][t];
+    if (t == 0) a.block_keep[blockIdx.x] = v;
+    else a.block_stat[2 * (size_t)blockIdx.x + (t - 1)] = v;
+  }
+}
+
+void launch_adapt_restore(hipStream_t st, const AdaptParams& ap) {
+  hipLaunchKernelGGL(k_adapt_select_state, dim3(ap.blocks), dim3(BLOCK), 0, st, ap);
+  hipLaunchKernelGGL(k_adapt_scan, dim3(1), dim3(BLOCK), 0, st, ap);
+  hipLaunchKernelGGL(k_adapt_scatter, dim3(ap.blocks), dim3(BLOCK), 0, st, ap);
+}
+
 void launch_adapt(hipStream_t st, const AdaptParams& ap) {
   hipLaunchKernelGGL(k_adapt_select, dim3(ap.blocks), dim3(BLOCK), 0, st, ap);
   hipLaunchKernelGGL(k_adapt_scan, dim3(1), dim3(BLOCK), 0, st, ap);

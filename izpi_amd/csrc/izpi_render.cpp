@@ -12,6 +12,17 @@
 //               [--progressive STEP --noise-threshold T [--noise-tolerated F] [--noise-floor L]
 //                [--min-samples K] [--noise-out se.pfm] [--adaptive [--samples-out n.pfm]]
 //                [--denoise-variance [N] [--denoise-sigma c,n,a] [--variance-floor F] [--variance-out v.pfm]]]
+//               [--progressive STEP [--stop-after K] [--checkpoint FILE] [--resume FILE]]
+//
+// --checkpoint FILE (with --progressive STEP) writes the session's checkpoint (DESIGN.md section
+// 3.11, izpi_gpu_progressive_checkpoint) when the run ends, through a temporary file and a rename;
+// --stop-after K ends the run after K steps, which is how a job with a time limit renders a part
+// of a frame; --resume FILE continues the session FILE holds under this command's scene, size,
+// sampler and seed (--samples, the cap, and STEP may be new). The three need --progressive, and
+// --noise-threshold / --adaptive must be given as the interrupted run had them. One
+//   IZPI_CHECKPOINT read|wrote file= bytes= done=
+// line is printed per file. The files a resumed run writes are, byte for byte, those of the
+// run that was never interrupted.
 //
 // --denoise [N] (--sampler colour or spectral) filters the frame with N iterations (default
 // IZPI_DENOISE_DEFAULT_ITERATIONS) of the edge-avoiding a-trous denoiser (izpi_gpu_denoise,
@@ -134,6 +145,8 @@ int main(int argc, char** argv) {
   std::string noise_out, samples_out;
   bool adaptive = false;
   double ink[3] = {0.0, 0.0, 0.0};
+  std::string ckpt_out, ckpt_in;
+  uint32_t stop_after = 0;
   bool quantized = false;
   uint32_t W = 1024, H = 1024, spp = 16, depth = 50, device = 0, gpus = 1;
   uint64_t seed = 12345;
@@ -182,6 +195,9 @@ int main(int argc, char** argv) {
     else if (a == "--noise-out") noise_out = val();
     else if (a == "--adaptive") adaptive = true;
     else if (a == "--samples-out") samples_out = val();
+    else if (a == "--checkpoint") ckpt_out = val();
+    else if (a == "--resume") ckpt_in = val();
+    else if (a == "--stop-after") { stop_after = (uint32_t)atoi(val().c_str()); if (!stop_after) die("--stop-after takes at least 1 step"); }
     else if (a == "--ink") { if (sscanf(val().c_str(), "%lf,%lf,%lf", &ink[0], &ink[1], &ink[2]) != 3) die("--ink takes r,g,b"); }
     else die("unknown option " + a);
   }
@@ -190,6 +206,9 @@ int main(int argc, char** argv) {
   if (acc != "forward" && acc != "recursive") die("--accumulation must be forward or recursive");
   if (!snap_prefix.empty() && !progressive) die("--snapshots needs --progressive");
   if (noise && !progressive) die("--noise-threshold needs --progressive");
+  if (!ckpt_out.empty() && !progressive) die("--checkpoint needs --progressive");
+  if (!ckpt_in.empty() && !progressive) die("--resume needs --progressive");
+  if (stop_after && !progressive) die("--stop-after needs --progressive");
   if (!noise_out.empty() && !noise) die("--noise-out needs --noise-threshold");
   if (adaptive && !noise) die("--adaptive needs --progressive and --noise-threshold");
   if (!samples_out.empty() && !adaptive) die("--samples-out needs --adaptive");
@@ -326,11 +345,31 @@ int main(int argc, char** argv) {
     // the frame in steps; a snapshot after each (the last one is the frame)
     auto ok = [&](int r) { if (r) die(multi ? izpi_gpu_multi_last_error(multi) : izpi_gpu_last_error(ctx)); };
     const uint32_t flags = (noise ? (uint32_t)IZPI_PROG_NOISE : 0u) | (adaptive ? (uint32_t)IZPI_PROG_ADAPTIVE : 0u);
-    ok(multi ? izpi_gpu_multi_progressive_begin_ex(multi, &req, progressive, flags) : izpi_gpu_progressive_begin_ex(ctx, &req, progressive, flags));
+    uint64_t scene_tag = 0;
+    if (izpi_host_scene_tag(izpi_host_scene_desc(host), &scene_tag)) die(izpi_host_last_error());
+    uint32_t done0 = 0;
+    if (!ckpt_in.empty()) {  // continue the session the file holds
+      std::vector<char> blob;
+      if (!read_file(ckpt_in, blob)) die("cannot read " + ckpt_in);
+      uint64_t bflags = 0, bdone = 0;
+      if (izpi_host_checkpoint_field(blob.data(), blob.size(), IZPI_CKPT_FLAGS, &bflags) ||
+          izpi_host_checkpoint_field(blob.data(), blob.size(), IZPI_CKPT_DONE, &bdone))
+        die(izpi_host_last_error());
+      if (bflags != flags) die("--resume: the checkpoint's session was begun with other --noise-threshold / --adaptive options");
+      ok(multi ? izpi_gpu_multi_progressive_resume(multi, &req, progressive, scene_tag, blob.data(), blob.size())
+               : izpi_gpu_progressive_resume(ctx, &req, progressive, scene_tag, blob.data(), blob.size()));
+      done0 = (uint32_t)bdone;
+      fprintf(stderr, "IZPI_CHECKPOINT read file=%s bytes=%llu done=%u\n", ckpt_in.c_str(), (unsigned long long)blob.size(), done0);
+    } else {
+      ok(multi ? izpi_gpu_multi_progressive_begin_ex(multi, &req, progressive, flags) : izpi_gpu_progressive_begin_ex(ctx, &req, progressive, flags));
+    }
     bool stop = false;
-    for (uint32_t done = 0; done < spp && !stop;) {
+    uint32_t steps = 0, last_done = done0;
+    for (uint32_t done = done0; done < spp && !stop;) {
       ok(multi ? izpi_gpu_multi_progressive_step(multi, 0, stv.data()) : izpi_gpu_progressive_step(ctx, 0, stv.data()));
       done = done + progressive < spp ? done + progressive : spp;
+      last_done = done;
+      const bool interrupted = stop_after && ++steps >= stop_after;  // --stop-after: the run ends here, the frame as it stands
       if (adaptive && done >= (nparams.min_spp > 2 ? nparams.min_spp : 2u)) {  // ... and its rule on an adaptive session
         izpi_adapt_stats as;
         ok(multi ? izpi_gpu_multi_progressive_adapt(multi, &nparams, &as) : izpi_gpu_progressive_adapt(ctx, &nparams, &as));
@@ -348,7 +387,7 @@ int main(int argc, char** argv) {
                 fin ? ns.sum_error / (double)fin : 0.0);
         stop = ns.converged != 0;
       }
-      if (stop || done == spp) {
+      if (stop || done == spp || interrupted) {
         spent = done;
         if (!noise_out.empty() && done >= 2) {
           std::vector<double> se((size_t)W * H * 4);
@@ -369,10 +408,22 @@ int main(int argc, char** argv) {
           write_pfm(samples_out, map, W, H);
         }
       }
-      if (snap_prefix.empty() && done < spp && !stop) continue;
+      if (snap_prefix.empty() && done < spp && !stop && !interrupted) continue;
       ok(multi ? izpi_gpu_multi_progressive_snapshot(multi, IZPI_SNAP_CANVAS, canvas.data())
                : izpi_gpu_progressive_snapshot(ctx, IZPI_SNAP_CANVAS, canvas.data()));
       if (!snap_prefix.empty()) write_pfm(snap_prefix + "_" + std::to_string(done) + ".pfm", canvas, W, H);
+      if (interrupted) break;
+    }
+    if (!ckpt_out.empty()) {  // the session as the run leaves it, through a temporary file and a rename
+      uint64_t n = 0;
+      ok(multi ? izpi_gpu_multi_progressive_checkpoint_bytes(multi, &n) : izpi_gpu_progressive_checkpoint_bytes(ctx, &n));
+      std::vector<char> blob(n);
+      ok(multi ? izpi_gpu_multi_progressive_checkpoint(multi, scene_tag, blob.data(), n) : izpi_gpu_progressive_checkpoint(ctx, scene_tag, blob.data(), n));
+      const std::string tmp = ckpt_out + ".tmp";
+      FILE* f = fopen(tmp.c_str(), "wb");
+      if (!f || fwrite(blob.data(), 1, blob.size(), f) != blob.size() || fclose(f) != 0 || rename(tmp.c_str(), ckpt_out.c_str()) != 0)
+        die("cannot write " + ckpt_out);
+      fprintf(stderr, "IZPI_CHECKPOINT wrote file=%s bytes=%llu done=%u\n", ckpt_out.c_str(), (unsigned long long)n, last_done);
     }
     ok(multi ? izpi_gpu_multi_progressive_end(multi) : izpi_gpu_progressive_end(ctx));
   } else if (multi) {

@@ -6,8 +6,9 @@
 //   session.hip     progressive sessions on one context, their noise estimate and stop rule;
 //   multi.hip       the share plan, device groups in one process (and their sessions), RCCL ranks;
 //   components.hip  post-processing and the component entries the tests call;
-//   trace.hip, wavefront.hip, preview.hip, resolve.hip, noise.hip, adapt.hip, denoise.hip:
-//   the kernels a render or a filter runs, each with its launch code.
+//   trace.hip, wavefront.hip, preview.hip, resolve.hip, noise.hip, adapt.hip, denoise.hip,
+//   checkpoint.hip: the kernels a render, a filter or a session's checkpoint runs, each with
+//   its launch code.
 // The shade_*.hip units need none of this (izpi_kern.h). Not part of the ABI.
 #pragma once
 #include <atomic>
@@ -22,6 +23,7 @@
 #include "izpi_kern.h"
 #include "izpi_req.h"
 #include "pixel_map.h"
+#include "checkpoint.h"
 #include "render_plan.h"
 
 namespace izpi_bvh {  // bvh_build.hip
@@ -91,6 +93,34 @@ struct AdaptParams {
   uint32_t* totals;       // [4]: active, counted, non-finite, 0
 };
 void launch_adapt(hipStream_t st, const AdaptParams& ap);
+// ... and a resumed session's active list from the state bytes a checkpoint stored: k_adapt_select_state
+// counts where k_adapt_select evaluates the rule (retirement is final, and the thresholds of the
+// earlier adapt calls are not stored), then k_adapt_scan and k_adapt_scatter as they are.
+void launch_adapt_restore(hipStream_t st, const AdaptParams& ap);
+// k_ckpt_gather, k_ckpt_scatter and k_ckpt_claimed (checkpoint.hip): a
+// session's state between the packed order of its tiles and the frame-order planes of a
+// checkpoint in the context's staging buffer (d_ckpt: CkptBufs).
+struct CkptParams {
+  PixelMap map;
+  ck::Packed packed;
+  ck::Planes planes;
+  uint32_t* block_counts;  // k_ckpt_scatter: [ceil(num_pixels / 256)] pixels without a record; k_ckpt_claimed: [ceil(W * H / 256)] claimed records
+};
+void launch_ckpt_gather(hipStream_t st, const CkptParams& cp);
+void launch_ckpt_scatter(hipStream_t st, const CkptParams& cp);
+void launch_ckpt_claimed(hipStream_t st, const CkptParams& cp);
+// d_ckpt for a W x H frame and a session of `pixels` pixels: the blob's planes as they lie behind
+// its header (one copy moves them), the claimed marks, the blocks' counts.
+struct CkptBufs {
+  size_t planes, claimed, block_counts, bytes;
+  CkptBufs(const ck::Layout& l, size_t pixels) {
+    auto up = [](size_t v) { return (v + 15) / 16 * 16; };
+    planes = 0;
+    claimed = up(l.bytes - sizeof(ck::Header));
+    block_counts = claimed + up(l.n);
+    bytes = block_counts + up(((std::max<size_t>(pixels, l.n) + 255) / 256) * 4);
+  }
+};
 // d_adapt of `pixels` pixels: the five arrays above at 16-B aligned offsets.
 struct AdaptBufs {
   size_t counts, state, table, block_keep, block_stat, totals, bytes;
@@ -180,6 +210,8 @@ struct izpi_ctx {
   double* d_noisepart = nullptr; size_t noisepart_cap = 0;  // k_noise_stats' block partials: [blocks] sums, then [blocks][4] counts
   // a session begun with IZPI_PROG_ADAPTIVE (adapt.hip; AdaptBufs; as above, it only grows and no plan counts it):
   char* d_adapt = nullptr; size_t adapt_cap = 0;  // the per-pixel sample counts, the retirements, the active list
+  // a session's checkpoint or resume (checkpoint.hip; CkptBufs): allocated by the first of either, it only grows
+  char* d_ckpt = nullptr; size_t ckpt_cap = 0;
   uint32_t* h_count = nullptr;                        // pinned readback of d_misc (unit head, queue lengths; same stride) + scratch
   hipEvent_t ev3 = nullptr;
   hipEvent_t evb[3 * IZPI_PASS_BATCH] = {};
@@ -389,6 +421,13 @@ int session_step(izpi_ctx* ctx, uint32_t spp, izpi_render_stats* stats);
 int session_noise(izpi_ctx* ctx, const izpi_noise_params* params, izpi_noise_stats* out);
 int session_adapt(izpi_ctx* ctx, const izpi_noise_params* params, izpi_adapt_stats* out);
 int session_snapshot(izpi_ctx* ctx, uint32_t form, double* out_dev);
+// The session's checkpoint into out_host (cap bytes), and a session begun from one. share: a
+// device of a group installs its own share's pixels: records of other shares may be left over
+// (the group checks the frame's pixel set), and the counters are the blob's or (zero_counters) zero.
+int session_checkpoint_bytes(izpi_ctx* ctx, uint64_t* bytes);
+int session_checkpoint(izpi_ctx* ctx, uint64_t scene_tag, void* out_host, uint64_t cap);
+int session_resume(izpi_ctx* ctx, const izpi_render_req* req, uint32_t step_spp, uint64_t scene_tag, const void* blob,
+                   uint64_t bytes, bool share = false, bool zero_counters = false);
 // The checks a context's session and a group's share (each true / false with the message in err).
 bool session_lacks_noise(const izpi_ctx::Session& ss, std::string& err, uint32_t need = 2);
 bool noise_params_ok(const izpi_noise_params* params, izpi_noise_params& p, std::string& err);

@@ -475,6 +475,136 @@ int izpi_gpu_multi_progressive_converge(izpi_multi* m, const izpi_noise_params* 
                        [&]() { return m->session.done; }, noise);
 }
 
+// ---- checkpoint and resume of the group's session
+int izpi_gpu_multi_progressive_checkpoint_bytes(izpi_multi* m, uint64_t* bytes) {
+  if (!multi_in_session(m)) return IZPI_ERR_INVALID;
+  if (!bytes) { m->err = "null output"; return IZPI_ERR_INVALID; }
+  const izpi_ctx::Session& ms = m->session;
+  *bytes = ck::Layout(ms.req.width, ms.req.height, (ms.noise ? (uint32_t)IZPI_PROG_NOISE : 0u) | (ms.adaptive ? (uint32_t)IZPI_PROG_ADAPTIVE : 0u)).bytes;
+  return IZPI_OK;
+}
+
+// One blob for the frame: every device exports its share's blob (the frame's planes with its own
+// pixels present), and the host copies each present record into the caller's. The shares are
+// disjoint but for pixels of overlapping tiles, whose records are equal. The header's integers
+// and counters are the devices' sums, done is the group's.
+int izpi_gpu_multi_progressive_checkpoint(izpi_multi* m, uint64_t scene_tag, void* out_host, uint64_t cap) {
+  if (!multi_in_session(m)) return IZPI_ERR_INVALID;
+  const izpi_ctx::Session& ms = m->session;
+  if (!out_host) { m->err = "null output"; return IZPI_ERR_INVALID; }
+  if (ms.done == 0) { m->err = "checkpoint: before the session's first sample (done == 0)"; return IZPI_ERR_INVALID; }
+  const uint32_t flags = (ms.noise ? (uint32_t)IZPI_PROG_NOISE : 0u) | (ms.adaptive ? (uint32_t)IZPI_PROG_ADAPTIVE : 0u);
+  const ck::Layout l(ms.req.width, ms.req.height, flags);
+  if (cap < l.bytes) {
+    m->err = "checkpoint: the output holds " + std::to_string(cap) + " bytes, the blob takes " + std::to_string(l.bytes);
+    return IZPI_ERR_INVALID;
+  }
+  std::vector<std::vector<char>> part(m->ctx.size());
+  for (size_t i = 0; i < part.size(); i++)
+    if (m->ctx[i]->session.open) part[i].resize(l.bytes);
+  const int rc = on_every_device(m, [&](uint32_t i, izpi_ctx* c) {
+    return c->session.open ? session_checkpoint(c, scene_tag, part[i].data(), l.bytes) : (int)IZPI_OK;
+  });
+  if (rc) return rc;
+  char* out = (char*)out_host;
+  memset(out, 0, l.bytes);
+  const ck::Planes f = ck::planes_at(out, 0, l);
+  memset(f.state, ck::NOT_IN_SESSION, l.n);
+  ck::Header h = checkpoint_header(ms.req, flags, scene_tag);
+  h.cnt_n = CNT_N;
+  for (std::vector<char>& b : part) {
+    if (b.empty()) continue;
+    ck::Header d;
+    memcpy(&d, b.data(), sizeof d);
+    h.listed |= d.listed; h.samples += d.samples; h.active += d.active;
+    for (uint32_t k = 0; k < CNT_N; k++) h.counters[k] += d.counters[k];
+    const ck::Planes s = ck::planes_at(b.data(), 0, l);
+    for (uint64_t i = 0; i < l.n; i++) {
+      if (s.state[i] == ck::NOT_IN_SESSION) continue;
+      f.state[i] = s.state[i];
+      memcpy(f.sums + 3 * i, s.sums + 3 * i, 24);
+      if (f.moments) memcpy(f.moments + 3 * i, s.moments + 3 * i, 24);
+      if (f.counts) f.counts[i] = s.counts[i];
+    }
+  }
+  for (uint64_t i = 0; i < l.n; i++) h.pixels += f.state[i] != ck::NOT_IN_SESSION;
+  h.done = ms.done;
+  memcpy(out, &h, sizeof h);
+  h.checksum = checkpoint_checksum(out, l.bytes);
+  memcpy(out, &h, sizeof h);
+  return IZPI_OK;
+}
+
+// begin_ex's checks and share plan with the blob's flags; every device resumes the pixels of its
+// own share (session_resume's share form: it refuses a pixel without a record), and the first
+// device with a share takes the stored counters, so that the devices' sums run on. Whether a
+// record belongs to no pixel of the frame is checked here, on the host, over the units: the
+// devices' marks would have to be merged first.
+int izpi_gpu_multi_progressive_resume(izpi_multi* m, const izpi_render_req* req, uint32_t step_spp, uint64_t scene_tag,
+                                      const void* blob, uint64_t bytes) {
+  if (!multi_valid(m)) return IZPI_ERR_INVALID;
+  if (m->prog_open) { m->err = "a progressive session is already open"; return IZPI_ERR_INVALID; }
+  if (!req || step_spp == 0) { m->err = "progressive_resume: a request and step_spp >= 1"; return IZPI_ERR_INVALID; }
+  for (izpi_ctx* c : m->ctx)
+    if (c->session.open) { m->err = "a context of this group has a progressive session of its own"; return IZPI_ERR_INVALID; }
+  char msg[160];
+  if (const char* bad = checkpoint_check(blob, bytes, req, scene_tag, msg, sizeof msg)) { m->err = bad; return IZPI_ERR_INVALID; }
+  ck::Header h;
+  memcpy(&h, blob, sizeof h);
+  int rc = session_copy_request(m->session, req, m->err);
+  if (rc) return rc;
+  izpi_ctx::Session& ms = m->session;
+  auto fail = [&](int status) {
+    for (izpi_ctx* c : m->ctx) session_drop(c);
+    ms = izpi_ctx::Session{};
+    return status;
+  };
+  if (ms.req.post != IZPI_POST_NONE && ms.req.num_tiles != 0) {
+    m->err = "post-processing needs a whole-frame request";
+    return fail(IZPI_ERR_INVALID);
+  }
+  ms.step_spp = std::min(step_spp, ms.req.spp);
+  Shares sh;
+  if ((rc = multi_shares(m, &ms.req, sh))) return fail(rc);
+  const ck::Layout l(h.width, h.height, h.flags);
+  {
+    std::vector<uint8_t> mine(l.n, 0);
+    for (size_t u = 0; u < sh.all.size() / 4; u++)
+      for (uint32_t y = sh.all[4 * u + 1]; y <= sh.all[4 * u + 3]; y++)
+        for (uint32_t x = sh.all[4 * u]; x <= sh.all[4 * u + 2]; x++) mine[(size_t)y * h.width + x] = 1;
+    const uint8_t* state = (const uint8_t*)blob + l.state;
+    uint64_t absent = 0, unclaimed = 0;
+    for (uint64_t i = 0; i < l.n; i++) {
+      absent += mine[i] && state[i] == ck::NOT_IN_SESSION;
+      unclaimed += !mine[i] && state[i] != ck::NOT_IN_SESSION;
+    }
+    if (absent || unclaimed) {
+      m->err = absent ? "checkpoint: " + std::to_string(absent) + " pixels of the request have no record in it (the pixel sets differ)"
+                      : "checkpoint: " + std::to_string(unclaimed) + " of its records belong to no pixel of the request (the pixel sets differ)";
+      return fail(IZPI_ERR_INVALID);
+    }
+  }
+  uint32_t first = (uint32_t)m->ctx.size();
+  for (uint32_t i = 0; i < m->ctx.size() && first == m->ctx.size(); i++)
+    if (!sh.mine(i).empty()) first = i;
+  rc = on_every_device(m, [&](uint32_t i, izpi_ctx* c) {
+    const int r = share_buffers(c, sh, false);
+    if (r) return r;
+    const std::vector<uint32_t> mine = sh.mine(i);
+    if (mine.empty()) return (int)IZPI_OK;
+    const izpi_render_req q = share_request(ms.req, mine);
+    return session_resume(c, &q, ms.step_spp, scene_tag, blob, bytes, true, i != first);
+  });
+  if (rc) return fail(rc);
+  ms.noise = (h.flags & IZPI_PROG_NOISE) != 0;
+  ms.adaptive = (h.flags & IZPI_PROG_ADAPTIVE) != 0;
+  ms.listed = h.listed != 0; ms.active = (uint32_t)h.active;
+  ms.done = h.done;
+  m->shares = sh;
+  m->prog_open = true;
+  return IZPI_OK;
+}
+
 int izpi_gpu_multi_progressive_end(izpi_multi* m) {
   if (!multi_in_session(m)) return IZPI_ERR_INVALID;
   for (izpi_ctx* c : m->ctx) session_drop(c);

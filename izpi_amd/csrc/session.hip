@@ -292,6 +292,175 @@ int session_snapshot(izpi_ctx* ctx, uint32_t form, double* out_dev) {
   return IZPI_OK;
 }
 
+// ---- checkpoint and resume
+static uint32_t session_flags(const izpi_ctx::Session& ss) {
+  return (ss.noise ? (uint32_t)IZPI_PROG_NOISE : 0u) | (ss.adaptive ? (uint32_t)IZPI_PROG_ADAPTIVE : 0u);
+}
+
+// The staging buffer for the session's frame (grown on the first checkpoint or resume of its
+// size, never by a session that does neither), the session's tiles on the device, and the
+// kernels' view of both.
+static int ckpt_params(izpi_ctx* ctx, const ck::Layout& l, CkptParams* cp) {
+  const izpi_ctx::Session& ss = ctx->session;
+  const CkptBufs cb(l, ss.num_pixels);
+  int rc = grow(ctx, (void**)&ctx->d_ckpt, &ctx->ckpt_cap, cb.bytes);
+  if (!rc) rc = session_tiles(ctx);
+  if (rc) return rc;
+  cp->map = session_view(ctx).map;
+  cp->planes = ck::planes_at(ctx->d_ckpt + cb.planes, sizeof(ck::Header), l, (uint8_t*)(ctx->d_ckpt + cb.claimed));
+  cp->block_counts = (uint32_t*)(ctx->d_ckpt + cb.block_counts);
+  return IZPI_OK;
+}
+
+// The sum of the first `blocks` words of cp.block_counts, on the host (integers: no order matters).
+static int ckpt_block_total(izpi_ctx* ctx, const CkptParams& cp, size_t blocks, uint64_t* total) {
+  std::vector<uint32_t> part(blocks);
+  HIP_TRY(hipMemcpyAsync(part.data(), cp.block_counts, blocks * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  *total = 0;
+  for (uint32_t v : part) *total += v;
+  return IZPI_OK;
+}
+
+int session_checkpoint_bytes(izpi_ctx* ctx, uint64_t* bytes) {
+  if (!ctx->session.open) { ctx->err = "no progressive session is open"; return IZPI_ERR_INVALID; }
+  if (!bytes) { ctx->err = "null output"; return IZPI_ERR_INVALID; }
+  *bytes = ck::Layout(ctx->session.req.width, ctx->session.req.height, session_flags(ctx->session)).bytes;
+  return IZPI_OK;
+}
+
+// checkpoint: the planes are zeroed with every record absent, k_ckpt_gather writes the session's
+// pixels, and one copy moves them behind the header in the caller's memory; the header is
+// written last, with the checksum of what lies behind it. Nothing of the session is written.
+int session_checkpoint(izpi_ctx* ctx, uint64_t scene_tag, void* out_host, uint64_t cap) {
+  int rc = session_usable(ctx);
+  if (rc) return rc;
+  const izpi_ctx::Session& ss = ctx->session;
+  if (!out_host) { ctx->err = "null output"; return IZPI_ERR_INVALID; }
+  if (ss.done == 0) { ctx->err = "checkpoint: before the session's first sample (done == 0)"; return IZPI_ERR_INVALID; }
+  const uint32_t flags = session_flags(ss);
+  const ck::Layout l(ss.req.width, ss.req.height, flags);
+  if (cap < l.bytes) {
+    ctx->err = "checkpoint: the output holds " + std::to_string(cap) + " bytes, the blob takes " + std::to_string(l.bytes);
+    return IZPI_ERR_INVALID;
+  }
+  CkptParams cp{};
+  if ((rc = ckpt_params(ctx, l, &cp))) return rc;
+  hipStream_t st = ctx->stream;
+  const size_t plane_bytes = l.bytes - sizeof(ck::Header);
+  HIP_TRY(hipMemsetAsync(ctx->d_ckpt, 0, plane_bytes, st));
+  HIP_TRY(hipMemsetAsync(cp.planes.state, ck::NOT_IN_SESSION, l.n, st));
+  const AdaptParams a = ss.listed ? adapt_arrays(ctx) : AdaptParams{};
+  cp.packed = ck::Packed{ctx->d_running, ss.noise ? ctx->d_moments : nullptr, a.counts, a.state, ss.done};
+  launch_ckpt_gather(st, cp);
+  HIP_TRY(hipGetLastError());
+  char* out = (char*)out_host;
+  unsigned long long cnt[CNT_N];
+  HIP_TRY(hipMemcpyAsync(out + sizeof(ck::Header), ctx->d_ckpt, plane_bytes, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(cnt, ctx->d_counters, sizeof(cnt), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  ck::Header h = checkpoint_header(ss.req, flags, scene_tag);
+  h.listed = ss.listed ? 1u : 0u;
+  const uint8_t* state = (const uint8_t*)(out + l.state);
+  for (uint64_t i = 0; i < l.n; i++) h.pixels += state[i] != ck::NOT_IN_SESSION;
+  h.done = ss.done; h.samples = ss.samples; h.active = ss.adaptive ? ss.active : 0;
+  h.cnt_n = CNT_N;
+  for (uint32_t k = 0; k < ck::CARRIED_COUNTERS; k++) h.counters[k] = cnt[k];  // (the diagnostics stay 0: checkpoint.h)
+  memcpy(out, &h, sizeof h);
+  h.checksum = checkpoint_checksum(out, l.bytes);
+  memcpy(out, &h, sizeof h);
+  return IZPI_OK;
+}
+
+// resume: the blob's own validation (checkpoint_check: no device work before it holds), begin
+// with the blob's flags, then the planes to the staging buffer and k_ckpt_scatter into the
+// session's arrays. The pixel sets are equal when no session pixel lacks a record and the
+// distinct records claimed (marked by the scatter, counted by k_ckpt_claimed) are as many as the
+// blob holds. An adaptive session's list is rebuilt from the stored state bytes.
+int session_resume(izpi_ctx* ctx, const izpi_render_req* req, uint32_t step_spp, uint64_t scene_tag, const void* blob,
+                   uint64_t bytes, bool share, bool zero_counters) {
+  if (ctx->session.open) { ctx->err = "a progressive session is already open"; return IZPI_ERR_INVALID; }
+  char msg[160];
+  if (const char* bad = checkpoint_check(blob, bytes, req, scene_tag, msg, sizeof msg)) { ctx->err = bad; return IZPI_ERR_INVALID; }
+  ck::Header h;
+  memcpy(&h, blob, sizeof h);
+  if (h.cnt_n != CNT_N) {
+    ctx->err = "checkpoint: it holds " + std::to_string(h.cnt_n) + " device counters, this library " + std::to_string((uint32_t)CNT_N);
+    return IZPI_ERR_INVALID;
+  }
+  int rc = session_begin(ctx, req, step_spp, h.flags);
+  if (rc) return rc;
+  izpi_ctx::Session& ss = ctx->session;
+  auto fail = [&](int status, const std::string& why) {
+    session_drop(ctx);
+    ctx->err = why;
+    return status;
+  };
+  const ck::Layout l(h.width, h.height, h.flags);
+  CkptParams cp{};
+  if ((rc = ckpt_params(ctx, l, &cp))) return fail(rc, ctx->err);
+  hipStream_t st = ctx->stream;
+  const size_t plane_bytes = l.bytes - sizeof(ck::Header);
+  const CkptBufs cb(l, ss.num_pixels);
+  const AdaptParams arrays = ss.adaptive ? adapt_arrays(ctx) : AdaptParams{};
+  cp.packed = ck::Packed{ctx->d_running, ss.noise ? ctx->d_moments : nullptr, arrays.counts, arrays.state, h.done};
+  uint64_t absent = 0, claimed = 0;
+  auto install = [&]() -> int {
+    HIP_TRY(hipMemcpyAsync(ctx->d_ckpt, (const char*)blob + sizeof(ck::Header), plane_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(ctx->d_ckpt + cb.claimed, 0, l.n, st));
+    launch_ckpt_scatter(st, cp);
+    HIP_TRY(hipGetLastError());
+    int r = ckpt_block_total(ctx, cp, ((size_t)ss.num_pixels + 255) / 256, &absent);
+    if (r || absent || share) return r;
+    launch_ckpt_claimed(st, cp);
+    HIP_TRY(hipGetLastError());
+    return ckpt_block_total(ctx, cp, (size_t)((l.n + 255) / 256), &claimed);
+  };
+  if ((rc = install())) return fail(rc, ctx->err);
+  if (absent)
+    return fail(IZPI_ERR_INVALID, "checkpoint: " + std::to_string(absent) + " pixels of the request have no record in it (the pixel sets differ)");
+  if (!share && claimed != h.pixels)
+    return fail(IZPI_ERR_INVALID, "checkpoint: " + std::to_string(h.pixels - claimed) + " of its records belong to no pixel of the request (the pixel sets differ)");
+  // the integers: Σ n_p over the session's pixels, from the blob's own counts
+  uint64_t samples = (uint64_t)h.done * ss.num_pixels;
+  uint32_t active = 0;
+  if (ss.adaptive) {
+    const char* counts = (const char*)blob + l.counts;
+    samples = 0;
+    for (uint32_t p = 0; p < ss.num_pixels; p++) {
+      uint32_t x, y, n;
+      tile_pixel(ss.run_tiles.data(), ss.tile_w, ss.tile_h, p, &x, &y);
+      memcpy(&n, counts + 4 * ((size_t)y * h.width + x), sizeof n);
+      samples += n;
+    }
+    AdaptParams a = arrays;
+    a.view = session_view(ctx);
+    auto rebuild = [&]() -> int {
+      launch_adapt_restore(st, a);
+      HIP_TRY(hipGetLastError());
+      uint32_t totals[4] = {0, 0, 0, 0};
+      HIP_TRY(hipMemcpyAsync(totals, a.totals, sizeof(totals), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      active = totals[0];
+      return IZPI_OK;
+    };
+    if ((rc = rebuild())) return fail(rc, ctx->err);
+    if (!share && active != h.active) return fail(IZPI_ERR_INVALID, "checkpoint: its state bytes and its active count disagree");
+  }
+  if (!zero_counters) {
+    auto counters = [&]() -> int {
+      HIP_TRY(hipMemcpyAsync(ctx->d_counters, h.counters, CNT_N * sizeof(unsigned long long), hipMemcpyHostToDevice, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      return IZPI_OK;
+    };
+    if ((rc = counters())) return fail(rc, ctx->err);
+  }
+  ss.done = h.done; ss.samples = samples;
+  if (ss.adaptive) { ss.active = active; ss.listed = active < ss.num_pixels; }
+  ctx->prog_done.store(samples, std::memory_order_relaxed);
+  return IZPI_OK;
+}
+
 }  // namespace izpi_internal
 
 using namespace izpi_internal;
@@ -367,6 +536,25 @@ int izpi_gpu_progressive_snapshot(izpi_ctx* ctx, uint32_t form, double* out_host
   if ((rc = output_from_host(ctx, out_host, bytes))) return rc;
   if ((rc = session_snapshot(ctx, form, ctx->d_out))) return rc;
   return output_to_host(ctx, out_host, bytes);
+}
+
+int izpi_gpu_progressive_checkpoint_bytes(izpi_ctx* ctx, uint64_t* bytes) {
+  if (!ctx) return IZPI_ERR_INVALID;
+  return session_checkpoint_bytes(ctx, bytes);
+}
+
+int izpi_gpu_progressive_checkpoint(izpi_ctx* ctx, uint64_t scene_tag, void* out_host, uint64_t cap) {
+  if (!ctx) return IZPI_ERR_INVALID;
+  HIP_TRY(hipSetDevice(ctx->device));
+  return session_checkpoint(ctx, scene_tag, out_host, cap);
+}
+
+int izpi_gpu_progressive_resume(izpi_ctx* ctx, const izpi_render_req* req, uint32_t step_spp, uint64_t scene_tag,
+                                const void* blob, uint64_t bytes) {
+  if (!ctx) return IZPI_ERR_INVALID;
+  HIP_TRY(hipSetDevice(ctx->device));
+  if (!req || step_spp == 0) { ctx->err = "progressive_resume: a request and step_spp >= 1"; return IZPI_ERR_INVALID; }
+  return session_resume(ctx, req, step_spp, scene_tag, blob, bytes);
 }
 
 int izpi_gpu_progressive_end(izpi_ctx* ctx) {

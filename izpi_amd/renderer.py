@@ -28,6 +28,7 @@ import ctypes as C
 import numpy as np
 
 from . import _native as N
+from . import checkpoint
 from .scene import HostScene
 
 
@@ -284,10 +285,12 @@ class ProgressiveSession:
     bit for bit, that pixel of ``render(spp=its count)``. ``active``: the pixels still sampled
     (None before the first adapt()); ``done`` stops advancing once there is none."""
 
-    def __init__(self, owner, req, step_spp, noise=False, adaptive=False):
+    def __init__(self, owner, req, step_spp, noise=False, adaptive=False, resume=None):
         self._open = False
         if adaptive and not noise:
             raise ValueError("adaptive=True needs noise=True (IZPI_PROG_ADAPTIVE needs IZPI_PROG_NOISE)")
+        if resume is not None:
+            return self._resume(owner, req, step_spp, resume)
         self._owner = owner
         self._req = req  # (the library keeps its own copy; this one sizes the snapshots)
         self.step_spp = int(step_spp)
@@ -304,8 +307,40 @@ class ProgressiveSession:
             self._call("begin", C.byref(req), self.step_spp)
         self._open = True
 
+    def _resume(self, owner, req, step_spp, resume):
+        """The session a checkpoint (bytes or a path) holds, continued under `req` (DESIGN.md
+        3.11): whether it keeps a noise estimate and is adaptive is the checkpoint's to say."""
+        blob = checkpoint.load(resume)
+        info = checkpoint.checkpoint_info(blob)
+        self._owner = owner
+        self._req = req
+        self.step_spp = int(step_spp)
+        self.total = int(req.spp)
+        self.stats = self.noise_stats = self.adapt_stats = None
+        self._call("resume", C.byref(req), self.step_spp, owner.scene_tag, blob, len(blob))
+        self._open = True
+        self.done = info["done"]
+        self.adaptive = info["adaptive"]
+        self.active = info["active"] if self.adaptive else None
+
     def _call(self, what, *args):
         self._owner._call("progressive_" + what, *args)
+
+    def checkpoint(self):
+        """izpi_gpu_progressive_checkpoint: the session's state as one self-describing blob of
+        bytes, which ``progressive(..., resume=blob)`` of this or another
+        renderer of the same scene and frame continues, bit for bit the uninterrupted session,
+        in another process or over another number of GPUs. Legal after the first step; the
+        session goes on as it was."""
+        n = C.c_uint64()
+        self._call("checkpoint_bytes", C.byref(n))
+        buf = C.create_string_buffer(n.value)
+        self._call("checkpoint", self._owner.scene_tag, buf, n.value)
+        return buf.raw
+
+    def save(self, path):
+        """checkpoint() into the file `path`, through a temporary file and a rename."""
+        checkpoint.save(self.checkpoint(), path)
 
     def step(self, n=None):
         """Render the next n samples per pixel (None: step_spp), clipped to the cap; returns `done`."""
@@ -507,15 +542,26 @@ class _Renderer:
                             tiles, layout, post, self.tuning, self.accumulation, self.ink)
 
     # ------------------------------------------------------------- sessions
+    @property
+    def scene_tag(self):
+        """izpi_host_scene_tag of the host scene this renderer uploaded: what its sessions'
+        checkpoints carry and a resume compares. Computed on first use."""
+        if getattr(self, "_scene_tag_of", None) is not self.host:
+            self._scene_tag, self._scene_tag_of = checkpoint.scene_tag(self.host.desc), self.host
+        return self._scene_tag
+
     def progressive(self, step_spp, total=None, tiles=None, layout=N.OUT_CANVAS, post=N.POST_NONE, noise=False,
-                    adaptive=False):
+                    adaptive=False, resume=None):
         """Begin a progressive render of up to `total` samples per pixel (None: this
         renderer's spp) with a workspace sized for steps of `step_spp`: a ProgressiveSession
         (of a group: each device holds a session over its share). render(), prepare() and a
         scene upload are refused until it is closed. noise=True keeps the second moments the
         session's noise estimate needs (24 B per pixel more); adaptive=True (with it) lets
-        adapt() stop the sampling of converged pixels."""
-        return ProgressiveSession(self, self.request(tiles, layout, total, post), step_spp, noise, adaptive)
+        adapt() stop the sampling of converged pixels. resume: a checkpoint (the bytes of
+        ProgressiveSession.checkpoint(), or the path save() wrote) to continue instead of
+        starting at zero: noise and adaptive are then the checkpoint's; total (at least the
+        samples done), step_spp, layout, post and the tiles' order and shape may be new."""
+        return ProgressiveSession(self, self.request(tiles, layout, total, post), step_spp, noise, adaptive, resume)
 
     def render_adaptive(self, threshold, step_spp=16, max_spp=None, **params):
         """render_until with adaptive sampling: a pixel stops taking samples once its own
