@@ -111,7 +111,7 @@ static inline Vec3 Load(const double* p) { return V(p[0], p[1], p[2]); }
 
 // Go's int(float64) on amd64 (CVTTSD2SQ): NaN / out of range -> INT64_MIN.
 static inline int64_t go_int(double x) {
-  if (x != x || x >= 9223372036854775808.0 || x < -9223372036854775808.0) return INT64_MIN;
+  if (x != x || x >= 9223372036854775808.0 || x < -9223372036854775808.0) return INT64_MIN;  // [edge: go-int-range]
   return (int64_t)x;
 }
 
@@ -209,7 +209,7 @@ static void SampleWavelength(double random, double* lambda, double* pdf) {  // s
   for (int i = 0; i < ORACLE_CIE_N; i++) {
     double y = oracle_cie_y[i];
     if (current + y >= target) {
-      if (i > 0) {
+      if (i > 0) {  // [edge: sw-first-bucket]
         double prev = current;
         double t = (target - prev) / y;
         *lambda = oracle_cie_wavelengths[i - 1] + t * (oracle_cie_wavelengths[i] - oracle_cie_wavelengths[i - 1]);
@@ -228,7 +228,7 @@ static void SampleWavelength(double random, double* lambda, double* pdf) {  // s
 }
 
 static void GetCIEValues(double w, double* x, double* y, double* z) {  // spectral.go:227-253
-  if (w <= oracle_cie_wavelengths[0]) { *x = oracle_cie_x[0]; *y = oracle_cie_y[0]; *z = oracle_cie_z[0]; return; }
+  if (w <= oracle_cie_wavelengths[0]) { *x = oracle_cie_x[0]; *y = oracle_cie_y[0]; *z = oracle_cie_z[0]; return; }  // [edge: cie-low]
   if (w >= oracle_cie_wavelengths[ORACLE_CIE_N - 1]) {
     int l = ORACLE_CIE_N - 1; *x = oracle_cie_x[l]; *y = oracle_cie_y[l]; *z = oracle_cie_z[l]; return;
   }
@@ -255,10 +255,10 @@ struct ImageTex : Texture {  // image.go:73-101 (Float64NRGBA branch)
   Vec3 Value(double u, double v, Vec3) const override {
     int64_t i = go_int(u * (double)sizeX);
     int64_t j = go_int((1 - v) * ((double)sizeY - 0.001));
-    if (i < 0) i = 0;
-    if (j < 0) j = 0;
-    if (i > (int64_t)(sizeX - 1)) i = sizeX - 1;
-    if (j > (int64_t)(sizeY - 1)) j = sizeY - 1;
+    if (i < 0) i = 0;  // [edge: tex-i-low]
+    if (j < 0) j = 0;  // [edge: tex-j-low]
+    if (i > (int64_t)(sizeX - 1)) i = sizeX - 1;  // [edge: tex-i-high]
+    if (j > (int64_t)(sizeY - 1)) j = sizeY - 1;  // [edge: tex-j-high]
     const double* px = pix + ((size_t)j * sizeX + (size_t)i) * 4;
     return V(px[0], px[1], px[2]);
   }
@@ -310,12 +310,12 @@ struct SpectralImageTex : SpectralTexture {
       double falloff = go_exp(-(distance * distance) / (2.0 * width * width));
       spectralValue += b * falloff;
     }
-    if (go_abs(r - g) < 0.15 && go_abs(g - b) < 0.15 && go_abs(r - b) < 0.15) {
+    if (go_abs(r - g) < 0.15 && go_abs(g - b) < 0.15 && go_abs(r - b) < 0.15) {  // [edge: grey-rule]
       double maxRGB = go_max(r, go_max(g, b));
       spectralValue = go_max(spectralValue, maxRGB);
     }
     double maxRGB = go_max(r, go_max(g, b));
-    if (maxRGB > 0.7 && spectralValue < maxRGB * 0.8) spectralValue = go_max(spectralValue, maxRGB * 0.8);
+    if (maxRGB > 0.7 && spectralValue < maxRGB * 0.8) spectralValue = go_max(spectralValue, maxRGB * 0.8);  // [edge: bright-rule]
     return go_max(0.0, go_min(1.0, spectralValue));
   }
   void Build(int w, int h, const double* pix) {  // NewSpectralImageFromImage + transformRGBToSpectral
@@ -329,19 +329,19 @@ struct SpectralImageTex : SpectralTexture {
       }
   }
   int findWavelengthIndex(double lambda) const {
-    if (lambda < wavelengths[0]) return 0;
-    if (lambda > wavelengths.back()) return (int)wavelengths.size() - 1;
-    for (size_t i = 0; i < wavelengths.size(); i++)
+    if (lambda < wavelengths[0]) return 0;  // [edge: stex-lambda-low]
+    if (lambda > wavelengths.back()) return (int)wavelengths.size() - 1;  // [edge: stex-lambda-high]
+    for (size_t i = 0; i < wavelengths.size(); i++)  // [edge: stex-lambda-scan]
       if (lambda <= wavelengths[i]) return (int)i;
     return (int)wavelengths.size() - 1;
   }
   double Value(double u, double v, double lambda, Vec3) const override {
     int64_t i = go_int(u * (double)sizeX);
     int64_t j = go_int((1 - v) * ((double)sizeY - 0.001));
-    if (i < 0) i = 0;
-    if (j < 0) j = 0;
-    if (i > (int64_t)(sizeX - 1)) i = sizeX - 1;
-    if (j > (int64_t)(sizeY - 1)) j = sizeY - 1;
+    if (i < 0) i = 0;  // [edge: stex-i-low]
+    if (j < 0) j = 0;  // [edge: stex-j-low]
+    if (i > (int64_t)(sizeX - 1)) i = sizeX - 1;  // [edge: stex-i-high]
+    if (j > (int64_t)(sizeY - 1)) j = sizeY - 1;  // [edge: stex-j-high]
     const int64_t pixelIndex = j * sizeX + i;
     const int wi = findWavelengthIndex(lambda);
     if (wi < 0 || wi >= (int)data.size()) return 0.0;
@@ -534,8 +534,8 @@ struct Dielectric : Material {  // dielectric.go
     Ray scattered; bool isReflected;
     scatterCommon(r, hr, rnd, refIdx, scattered, isReflected);
     Vec3 att;
-    bool absNonZero = !(absorptionCoeff.X == 0 && absorptionCoeff.Y == 0 && absorptionCoeff.Z == 0);
-    if (computeBeerLambert && absNonZero && !isReflected) {
+    bool absNonZero = !(absorptionCoeff.X == 0 && absorptionCoeff.Y == 0 && absorptionCoeff.Z == 0);  // [edge: diel-abs-zero]
+    if (computeBeerLambert && absNonZero && !isReflected) {  // [edge: diel-beer]
       double pathLength = calculatePathLength(r, hr, scattered);
       att = V(go_exp(-absorptionCoeff.X * pathLength), go_exp(-absorptionCoeff.Y * pathLength), go_exp(-absorptionCoeff.Z * pathLength));
     } else {
@@ -552,7 +552,7 @@ struct Dielectric : Material {  // dielectric.go
     double albedo;
     if (!isReflected) {
       double pathLength = calculatePathLength(r, hr, scattered);
-      if (spectralAbsorptionCoeff) albedo = go_exp(-spectralAbsorptionCoeff->Value(hr.u, hr.v, lambda, hr.p) * pathLength);
+      if (spectralAbsorptionCoeff) albedo = go_exp(-spectralAbsorptionCoeff->Value(hr.u, hr.v, lambda, hr.p) * pathLength);  // [edge: sdiel-abs-tex]
       else albedo = 1.0;
     } else {
       albedo = 1.0;
@@ -703,7 +703,7 @@ struct Triangle : Hitable {  // triangle.go
     const double epsilon = 1e-8;
     Vec3 h = Cross(r.d, edge2);
     double a = Dot(edge1, h);
-    if (go_abs(a) < epsilon) return false;
+    if (go_abs(a) < epsilon) return false;  // [edge: tri-parallel]
     double f = 1.0 / a;
     Vec3 s = Sub(r.o, vertex0);
     u = f * Dot(s, h);
@@ -721,7 +721,7 @@ struct Triangle : Hitable {  // triangle.go
     if (!intersect(r, tMin, tMax, t, u, v)) return false;
     double w = 1.0 - u - v;
     double sum = u + v + w;
-    if (go_abs(sum - 1.0) > epsilon) { u /= sum; v /= sum; w /= sum; }
+    if (go_abs(sum - 1.0) > epsilon) { u /= sum; v /= sum; w /= sum; }  // [edge-unreachable: tri-renorm]
     double uu = w * u0 + u * u1 + v * u2;
     double vv = w * v0 + u * v1 + v * v2;
     Vec3 nrm = normal;
@@ -2179,6 +2179,12 @@ double oracle_spd_tabulated_value(const double* wl, const double* val, uint32_t 
 double oracle_spectral_value(int gaussian, double a, double b, double c, double lambda) {
   SpectralConstantTex t; t.peak = a; t.center = b; t.width = c; (void)gaussian;
   return t.Value(0, 0, lambda, Vec3());
+}
+// SpectralImage.Value (spectral_image.go:193-259) of a w x h NRGBA image at (u, v, lambda)
+double oracle_spectral_image_value(const double* pix, int w, int h, double u, double v, double lambda) {
+  SpectralImageTex t;
+  t.Build(w, h, pix);
+  return t.Value(u, v, lambda, Vec3());
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 """TEST INFRASTRUCTURE — ctypes binding of the CPU oracle (oracle/izpi_oracle.cpp).
 
-Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this
+Only tests/, __graft_entry__.smoke(), bench.py's cpu_baseline leg and the measuring tools
+(tools/oracle_coverage.py binds its instrumented build through use_library) may import this
 module; the product (izpi_amd) never does. The oracle is a deterministic CPU
 restatement of izpi's hot path (see the header of izpi_oracle.cpp for the
 reference file:line list it follows).
@@ -15,6 +16,7 @@ HERE = Path(__file__).resolve().parent
 LIB_PATH = HERE / "_build" / "liboracle.so"
 
 _lib = None
+_override = None  # use_library(): another build of the same source
 
 
 class OracleStats(C.Structure):
@@ -32,13 +34,23 @@ def build(force=False):
     return LIB_PATH
 
 
+def use_library(path):
+    """Bind another build of izpi_oracle.cpp (tools/oracle_coverage.py's instrumented one)
+    instead of _build/liboracle.so. Call it before the first lib(): the binding is made once."""
+    global _override
+    if _lib is not None:
+        raise RuntimeError("the oracle library is already loaded")
+    _override = Path(path)
+
+
 def lib():
     global _lib
     if _lib is not None:
         return _lib
-    build()
+    if _override is None:
+        build()
     from izpi_amd import _native as N  # struct layouts of the boundary headers only
-    L = C.CDLL(str(LIB_PATH))
+    L = C.CDLL(str(_override or LIB_PATH))
     L.oracle_build.argtypes = [C.POINTER(N.SceneInput)]
     L.oracle_build.restype = C.c_void_p
     L.oracle_error.argtypes = [C.c_void_p]
@@ -83,6 +95,8 @@ def lib():
     L.oracle_spectral_value.restype = C.c_double
     L.oracle_spd_tabulated_value.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_double]
     L.oracle_spd_tabulated_value.restype = C.c_double
+    L.oracle_spectral_image_value.argtypes = [C.POINTER(C.c_double), C.c_int, C.c_int, C.c_double, C.c_double, C.c_double]
+    L.oracle_spectral_image_value.restype = C.c_double
     L.oracle_tbn_mul.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.oracle_path_length.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.oracle_path_length.restype = C.c_double
