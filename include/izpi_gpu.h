@@ -301,7 +301,8 @@ int izpi_gpu_postprocess(izpi_ctx* ctx, double* canvas_dev, uint32_t width, uint
  * sigma_albedo^2)) with dc, dn, da the squared RGB distances to the centre in the three
  * frames. Pixels with alpha 0 (row 0, pixels outside the tiles) or a non-finite colour are
  * neither read as taps nor changed. Alpha is the centre's. iterations is 0..8 (0 copies);
- * every sigma is > 0 and may be +Inf (its term drops out); flags is 0. Anything else is
+ * every sigma is > 0 and may be +Inf (its term drops out); flags is 0 or
+ * IZPI_DENOISE_DEMODULATE (below; it needs the albedo canvas). Anything else is
  * IZPI_ERR_INVALID. p == NULL: the defaults below. normal / albedo may be NULL: the term is
  * left out. out may not overlap an input; width and height are at least 1.
  *
@@ -316,9 +317,24 @@ int izpi_gpu_postprocess(izpi_ctx* ctx, double* canvas_dev, uint32_t width, uint
  * Multi-GPU callers run it on izpi_gpu_multi_context(m, 0) over the gathered canvas. */
 typedef struct izpi_denoise_params {
   uint32_t iterations;
-  uint32_t flags; /* 0 */
+  uint32_t flags; /* 0 or IZPI_DENOISE_DEMODULATE */
   double sigma_colour, sigma_normal, sigma_albedo;
 } izpi_denoise_params;
+/* Albedo demodulation, an option of both filters: with this flag the
+ * filter runs on irradiance, colour / albedo, and the albedo is multiplied back afterwards, so
+ * texture detail is not smoothed. The albedo canvas is then required (it also stays the
+ * edge-stopping guide under sigma_albedo) and should come from at least as many samples as the
+ * frame. Channel k of a pixel is divided by m_k = its albedo when that is finite and greater
+ * than IZPI_DENOISE_ALBEDO_FLOOR (2^-10), by the floor otherwise (the albedo's alpha is
+ * ignored); the standard errors of the variance-guided filter are divided likewise, and V_0 is
+ * the squared length of the quotients. A pixel whose colour is not live is not divided. After
+ * the last iteration a pixel that was live in iteration 0 (its quotient live; its V_0 finite
+ * and >= 0) is multiplied by m_k; every other pixel of `out` is the input's four doubles, bit
+ * for bit. var_out is the variance of the filtered demodulated canvas, in the filter's own
+ * space: a scalar plane cannot be multiplied back per channel. iterations == 0 means what it
+ * means without the flag. Any other flag bit is refused. */
+#define IZPI_DENOISE_DEMODULATE 4u
+#define IZPI_DENOISE_ALBEDO_FLOOR 0.0009765625 /* 2^-10: dividing and multiplying by it is exact */
 #define IZPI_DENOISE_MAX_ITERATIONS 8
 #define IZPI_DENOISE_DEFAULT_ITERATIONS 5 /* sigma defaults 1.0, 0.5, 0.5: see DESIGN 3.8 */
 #define IZPI_DENOISE_DEFAULT_SIGMA_COLOUR 1.0
@@ -354,7 +370,7 @@ int izpi_gpu_denoise(izpi_ctx* ctx, const double* colour, const double* normal, 
  * is finite and > 0 (IZPI_DENOISE_VAR_DEFAULT_FLOOR: the chosen default; it keeps a pixel
  * whose samples happened to agree from freezing). stderr_dev is required; out may overlap
  * neither an input nor var_out. var_out ([H][W] float64, may be NULL) receives the variance
- * of the filtered canvas.
+ * of the filtered canvas (with IZPI_DENOISE_DEMODULATE: of the filtered demodulated canvas).
  *
  *  _denoise_var_device  all canvases and the plane in device memory. The colour ping-pong
  *                       shares the scratch canvas of _denoise_device; two variance planes

@@ -173,15 +173,17 @@ int izpi_host_displace(const izpi_tri_in* tris, uint64_t n, const double* rgba, 
 
 /* The host twin of izpi_gpu_denoise (izpi_gpu.h: the rule and the arguments are the same):
  * the sequential restatement from the same arithmetic (izpi_amd/csrc/denoise.h), bit for
- * bit what the device writes. All pointers host; its error is izpi_host_last_error's. */
+ * bit what the device writes, IZPI_DENOISE_DEMODULATE included (the demodulated canvas is
+ * a temporary). All pointers host; its error is izpi_host_last_error's. */
 int izpi_host_denoise(const double* colour, const double* normal, const double* albedo, double* out, uint32_t width,
                       uint32_t height, const izpi_denoise_params* p);
 
 /* The host twin of izpi_gpu_denoise_var (izpi_gpu.h: the rule and the arguments are the same;
  * the arithmetic is izpi_amd/csrc/denoise.h's), bit for bit what the device writes.
  * stderr_host: the [H][W][4] canvas of standard errors (IZPI_SNAP_NOISE's form); var_out
- * ([H][W], may be NULL): the variance of the filtered canvas. All pointers host; its error
- * is izpi_host_last_error's. */
+ * ([H][W], may be NULL): the variance of the filtered canvas (with IZPI_DENOISE_DEMODULATE:
+ * of the filtered demodulated canvas, the space the filter ran in). All pointers host; its
+ * error is izpi_host_last_error's. */
 int izpi_host_denoise_var(const double* colour, const double* stderr_host, const double* normal, const double* albedo,
                           double* out, double* var_out, uint32_t width, uint32_t height, const izpi_denoise_params* p,
                           double variance_floor);

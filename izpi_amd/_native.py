@@ -50,6 +50,8 @@ DENOISE_MAX_ITERATIONS = 8
 DENOISE_DEFAULT_ITERATIONS = 5
 DENOISE_DEFAULT_SIGMA_COLOUR, DENOISE_DEFAULT_SIGMA_NORMAL, DENOISE_DEFAULT_SIGMA_ALBEDO = 1.0, 0.5, 0.5
 DENOISE_VAR_DEFAULT_SIGMA_COLOUR, DENOISE_VAR_DEFAULT_FLOOR = 1.5, 1e-4  # the variance-guided filter's
+DENOISE_DEMODULATE = 4  # izpi_denoise_params.flags: filter colour / albedo, multiply back
+DENOISE_ALBEDO_FLOOR = 2.0 ** -10  # the least albedo a channel is divided by
 
 
 def prim_ref(kind, idx):
@@ -162,15 +164,18 @@ class DenoiseParams(C.Structure):
 
 
 def denoise_params(iterations=DENOISE_DEFAULT_ITERATIONS, sigma_colour=DENOISE_DEFAULT_SIGMA_COLOUR,
-                   sigma_normal=DENOISE_DEFAULT_SIGMA_NORMAL, sigma_albedo=DENOISE_DEFAULT_SIGMA_ALBEDO):
-    """izpi_denoise_params; the defaults are the library's (what a NULL pointer means)."""
-    return DenoiseParams(int(iterations), 0, float(sigma_colour), float(sigma_normal), float(sigma_albedo))
+                   sigma_normal=DENOISE_DEFAULT_SIGMA_NORMAL, sigma_albedo=DENOISE_DEFAULT_SIGMA_ALBEDO, demodulate=False):
+    """izpi_denoise_params; the defaults are the library's (what a NULL pointer means).
+    demodulate sets DENOISE_DEMODULATE: the call then needs the albedo canvas."""
+    return DenoiseParams(int(iterations), DENOISE_DEMODULATE if demodulate else 0, float(sigma_colour),
+                         float(sigma_normal), float(sigma_albedo))
 
 
 def denoise_var_params(iterations=DENOISE_DEFAULT_ITERATIONS, sigma_colour=DENOISE_VAR_DEFAULT_SIGMA_COLOUR,
-                       sigma_normal=DENOISE_DEFAULT_SIGMA_NORMAL, sigma_albedo=DENOISE_DEFAULT_SIGMA_ALBEDO):
+                       sigma_normal=DENOISE_DEFAULT_SIGMA_NORMAL, sigma_albedo=DENOISE_DEFAULT_SIGMA_ALBEDO,
+                       demodulate=False):
     """izpi_denoise_params with the variance-guided filter's defaults (what its NULL pointer means)."""
-    return denoise_params(iterations, sigma_colour, sigma_normal, sigma_albedo)
+    return denoise_params(iterations, sigma_colour, sigma_normal, sigma_albedo, demodulate)
 
 
 class NoiseParams(C.Structure):

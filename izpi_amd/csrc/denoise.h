@@ -16,6 +16,11 @@
 // pixel's standard errors, and every iteration carries it along with the squared weights
 // (it reads V_i and writes V_{i+1}), so the colour term narrows by itself as the image gets
 // smoother.
+//
+// Albedo demodulation (IZPI_DENOISE_DEMODULATE; section 3.8b, deviation A29) is an option of
+// both: demodulate() forms D_0 = C / m (and V_0 from S / m) ahead of iteration 0, the
+// iterations above run on it unchanged, and remodulate() multiplies m back after the last.
+// They are two passes of their own and pixel() knows nothing of them.
 #pragma once
 #include <stdint.h>
 
@@ -94,7 +99,8 @@ inline const char* check_args(bool var, const double* colour, const double* se, 
       (albedo && overlap(out, bytes, albedo, bytes)))
     return "denoise: out may not overlap an input canvas";
   if (p.iterations > IZPI_DENOISE_MAX_ITERATIONS) return "denoise: at most 8 iterations";
-  if (p.flags != 0) return "denoise: flags must be 0";
+  if (p.flags != 0 && p.flags != IZPI_DENOISE_DEMODULATE) return "denoise: flags must be 0";
+  if (p.flags && !albedo) return "denoise: demodulation needs the albedo canvas";
   if (!(p.sigma_colour > 0) || !(p.sigma_normal > 0) || !(p.sigma_albedo > 0))
     return "denoise: every sigma must be greater than 0 (+Inf drops its term)";
   if (!var) return nullptr;
@@ -133,6 +139,44 @@ IZPI_HD bool live(const double* px, double v) {
 IZPI_HD double dist2(const double* a, const double* b) {
   const double d0 = a[0] - b[0], d1 = a[1] - b[1], d2 = a[2] - b[2];
   return (d0 * d0 + d1 * d1) + d2 * d2;
+}
+
+// ---- albedo demodulation (IZPI_DENOISE_DEMODULATE)
+// Do this call's iterations run on the demodulated canvas? (With no iteration the flag changes
+// nothing: C is copied and V_0 is the colour's.)
+inline bool demodulates(const izpi_denoise_params& p) { return (p.flags & IZPI_DENOISE_DEMODULATE) && p.iterations > 0; }
+// m_k of an albedo channel: the albedo when it is a number above the floor, else the floor (a
+// power of two, so a black, negative, NaN or Inf albedo divides and multiplies back exactly).
+IZPI_HD double modulus(double a) { return finite(a) && a > IZPI_DENOISE_ALBEDO_FLOOR ? a : IZPI_DENOISE_ALBEDO_FLOOR; }
+// D_0 of a pixel into d (four doubles) from its colour c, standard errors s (VAR; else not
+// read: pass null) and albedo a: c / m when c is live, c as it is otherwise; alpha copied. The
+// return value is (VAR) V_0, variance0 of s / m.
+template <bool VAR>
+IZPI_HD double demodulate(const double* c, const double* s, const double* a, double* d) {
+  const double m[3] = {modulus(a[0]), modulus(a[1]), modulus(a[2])};
+  const bool alive = live<false>(c, 0.0);
+  for (int k = 0; k < 3; k++) d[k] = alive ? c[k] / m[k] : c[k];
+  d[3] = c[3];
+  if constexpr (VAR) {
+    const double q[3] = {s[0] / m[0], s[1] / m[1], s[2] / m[2]};
+    return variance0(q);
+  }
+  return 0.0;
+}
+// The pixel f of the last iteration's canvas back into colour, in place: f * m with the
+// centre's alpha when the pixel was live in iteration 0 (D_0 live, which a quotient that
+// overflowed is not, and (VAR) V_0 a number that can be a variance), else the input c, all
+// four doubles. The predicate is formed again from c, s and a, which no entry changes.
+template <bool VAR>
+IZPI_HD void remodulate(const double* c, const double* s, const double* a, double* f) {
+  double d[4];
+  const double v = demodulate<VAR>(c, s, a, d);
+  if (live<VAR>(d, v)) {
+    for (int k = 0; k < 3; k++) f[k] = f[k] * modulus(a[k]);
+    f[3] = c[3];
+  } else {
+    for (int k = 0; k < 4; k++) f[k] = c[k];
+  }
 }
 
 // The B3-spline row h = {1/16, 1/4, 3/8, 1/4, 1/16} at offset d = -2..2 (no table: nothing

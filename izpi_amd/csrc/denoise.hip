@@ -1,6 +1,7 @@
 // denoise.hip — the two a-trous denoisers on the device: the fixed-sigma filter (DESIGN.md
 // section 3.8: k_denoise, the izpi_gpu_denoise entries) and the variance-guided one (section
-// 3.8a: k_dnv_init, k_dnv, the izpi_gpu_denoise_var entries; include/izpi_gpu.h). The
+// 3.8a: k_dnv_init, k_dnv, the izpi_gpu_denoise_var entries; include/izpi_gpu.h), and for
+// both albedo demodulation (section 3.8b: k_demodulate, k_remodulate). The
 // arithmetic is denoise.h's, shared with the host twin (denoise_host.cpp), so both give the
 // same bits; the launch, the driver and the staging below are each written once for both.
 //
@@ -27,6 +28,50 @@ __global__ __launch_bounds__(kBlockX * kBlockY) void k_dnv_init(const double* S,
   for (uint64_t p = (uint64_t)blockIdx.x * (kBlockX * kBlockY) + threadIdx.x; p < pixels;
        p += (uint64_t)gridDim.x * (kBlockX * kBlockY))
     V[p] = dn::variance0(S + p * 4);
+}
+
+// IZPI_DENOISE_DEMODULATE (section 3.8b): D_0 = C / m into the context's d_demod ahead of
+// iteration 0, with VAR also V_0 from S / m (so that mode launches no k_dnv_init), and after
+// the last iteration the albedo back in place on the output. k_dnv_init's launch shape; the
+// inputs are read as pixel() reads them (plain doubles: they carry no alignment rule), the
+// two canvases written in two 16-byte stores per pixel. Each pass moves a few canvases once.
+__device__ inline void load_px(const double* at, double* px) {
+  for (int k = 0; k < 4; k++) px[k] = at[k];
+}
+__device__ inline void store_px(double* at, const double* px) {
+  double2* d = reinterpret_cast<double2*>(at);  // a pixel is 32 B, 32-B aligned
+  d[0] = make_double2(px[0], px[1]);
+  d[1] = make_double2(px[2], px[3]);
+}
+
+template <bool VAR>
+__global__ __launch_bounds__(kBlockX * kBlockY) void k_demodulate(const double* C, const double* S, const double* A, double* D,
+                                                                   double* V, uint64_t pixels) {
+  for (uint64_t p = (uint64_t)blockIdx.x * (kBlockX * kBlockY) + threadIdx.x; p < pixels;
+       p += (uint64_t)gridDim.x * (kBlockX * kBlockY)) {
+    double c[4], s[4] = {0, 0, 0, 0}, a[4], d[4];
+    load_px(C + p * 4, c);
+    load_px(A + p * 4, a);
+    if constexpr (VAR) load_px(S + p * 4, s);
+    const double v = dn::demodulate<VAR>(c, s, a, d);
+    store_px(D + p * 4, d);
+    if constexpr (VAR) V[p] = v;
+  }
+}
+
+template <bool VAR>
+__global__ __launch_bounds__(kBlockX * kBlockY) void k_remodulate(const double* C, const double* S, const double* A, double* out,
+                                                                   uint64_t pixels) {
+  for (uint64_t p = (uint64_t)blockIdx.x * (kBlockX * kBlockY) + threadIdx.x; p < pixels;
+       p += (uint64_t)gridDim.x * (kBlockX * kBlockY)) {
+    double c[4], s[4] = {0, 0, 0, 0}, a[4], f[4];
+    load_px(C + p * 4, c);
+    load_px(A + p * 4, a);
+    if constexpr (VAR) load_px(S + p * 4, s);
+    load_px(out + p * 4, f);
+    dn::remodulate<VAR>(c, s, a, f);
+    store_px(out + p * 4, f);
+  }
 }
 
 // The two kernels state their sweep themselves, k_dnv's being k_denoise's plus the variance
@@ -77,8 +122,9 @@ void launch(hipStream_t st, const double* src, const double* v, const double* nm
   });
 }
 
-// The *_device entries. The scratch canvas is there only when iterations > 1 and the planes
-// only when iterations > 0; both only grow: a smaller frame after a larger one reuses them.
+// The *_device entries. The scratch canvas is there only when iterations > 1, the planes only
+// when iterations > 0 and D_0's canvas only for a demodulating call; all three only grow: a
+// smaller frame after a larger one reuses them.
 template <bool VAR>
 int filter_device(izpi_ctx* ctx, const double* colour_dev, const double* stderr_dev, const double* normal_dev,
                   const double* albedo_dev, double* out_dev, double* var_out_dev, uint32_t width, uint32_t height,
@@ -101,17 +147,26 @@ int filter_device(izpi_ctx* ctx, const double* colour_dev, const double* stderr_
     const int rc = izpi_internal::grow(ctx, (void**)&ctx->d_dnvar, &ctx->dnvar_cap, 2 * pixels * sizeof(double));
     if (rc) return rc;
   }
+  const bool demod = dn::demodulates(p);
+  if (demod) {
+    const int rc = izpi_internal::grow(ctx, (void**)&ctx->d_demod, &ctx->demod_cap, bytes);
+    if (rc) return rc;
+  }
   double* const planes[2] = {VAR ? ctx->d_dnvar : nullptr, VAR && ctx->d_dnvar ? ctx->d_dnvar + pixels : nullptr};
   HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
+  const dim3 per_pixel((unsigned)std::min<uint64_t>(1u << 20, (pixels + kBlockX * kBlockY - 1) / (kBlockX * kBlockY)));
   // V_0: into plane 0, or with no iteration to come straight into the caller's plane
   double* const v0 = !VAR ? nullptr : p.iterations ? planes[0] : var_out_dev;
-  if (v0) {
-    const unsigned blocks = (unsigned)std::min<uint64_t>(1u << 20, (pixels + kBlockX * kBlockY - 1) / (kBlockX * kBlockY));
-    hipLaunchKernelGGL(k_dnv_init, dim3(blocks), dim3(kBlockX * kBlockY), 0, ctx->stream, stderr_dev, v0, (uint64_t)pixels);
+  if (demod) {  // D_0, and V_0 with it
+    hipLaunchKernelGGL(k_demodulate<VAR>, per_pixel, dim3(kBlockX * kBlockY), 0, ctx->stream, colour_dev, stderr_dev,
+                       albedo_dev, ctx->d_demod, v0, (uint64_t)pixels);
+    HIP_TRY(hipGetLastError());
+  } else if (v0) {
+    hipLaunchKernelGGL(k_dnv_init, per_pixel, dim3(kBlockX * kBlockY), 0, ctx->stream, stderr_dev, v0, (uint64_t)pixels);
     HIP_TRY(hipGetLastError());
   }
   if (p.iterations == 0) HIP_TRY(hipMemcpyAsync(out_dev, colour_dev, bytes, hipMemcpyDeviceToDevice, ctx->stream));
-  const double* src = colour_dev;
+  const double* src = demod ? ctx->d_demod : colour_dev;
   for (uint32_t i = 0; i < p.iterations; i++) {
     const bool last = i + 1 == p.iterations;
     double* dst = (p.iterations - 1 - i) % 2 == 0 ? out_dev : ctx->d_denoise;
@@ -120,6 +175,11 @@ int filter_device(izpi_ctx* ctx, const double* colour_dev, const double* stderr_
            dn::iteration<VAR>(p, variance_floor, i));
     HIP_TRY(hipGetLastError());
     src = dst;
+  }
+  if (demod) {  // the last iteration landed in out_dev
+    hipLaunchKernelGGL(k_remodulate<VAR>, per_pixel, dim3(kBlockX * kBlockY), 0, ctx->stream, colour_dev, stderr_dev,
+                       albedo_dev, out_dev, (uint64_t)pixels);
+    HIP_TRY(hipGetLastError());
   }
   HIP_TRY(hipEventRecord(ctx->ev1, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));

@@ -1,6 +1,6 @@
 // denoise_host.cpp — izpi_host_denoise and izpi_host_denoise_var: the two a-trous denoisers
 // on the host, the plain sequential form of the arithmetic in denoise.h (DESIGN.md sections
-// 3.8 and 3.8a). It is the twin the device path (denoise.hip) is tested against. No HIP
+// 3.8, 3.8a and, for IZPI_DENOISE_DEMODULATE, 3.8b). It is the twin the device path (denoise.hip) is tested against. No HIP
 // here: a host compiler builds it alone.
 #include <stdint.h>
 #include <string.h>
@@ -42,12 +42,20 @@ int filter(const double* colour, const double* se, const double* normal, const d
     if (VAR) {
       planes[0].resize(pixels);
       planes[1].resize(p.iterations ? pixels : 0);
-      for (size_t q = 0; q < pixels; q++) planes[0][q] = dn::variance0(se + q * 4);
+    }
+    // (IZPI_DENOISE_DEMODULATE) D_0, and V_0 of the demodulated standard errors with it
+    const bool demod = dn::demodulates(p);
+    std::vector<double> d0(demod ? doubles : 0);
+    for (size_t q = 0; q < pixels && (VAR || demod); q++) {
+      double v;
+      if (demod) v = dn::demodulate<VAR>(colour + q * 4, VAR ? se + q * 4 : nullptr, albedo + q * 4, d0.data() + q * 4);
+      else v = dn::variance0(se + q * 4);
+      if (VAR) planes[0][q] = v;
     }
     if (p.iterations == 0) memcpy(out, colour, doubles * sizeof(double));
     // ping-pong between `out` and one scratch canvas so that the last iteration lands in `out`
     std::vector<double> scratch(p.iterations > 1 ? doubles : 0);
-    const double* src = colour;
+    const double* src = demod ? d0.data() : colour;
     for (uint32_t i = 0; i < p.iterations; i++) {
       double* dst = (p.iterations - 1 - i) % 2 == 0 ? out : scratch.data();
       const double* v = planes[i % 2].data();
@@ -58,6 +66,8 @@ int filter(const double* colour, const double* se, const double* normal, const d
       });
       src = dst;
     }
+    for (size_t q = 0; q < pixels && demod; q++)
+      dn::remodulate<VAR>(colour + q * 4, VAR ? se + q * 4 : nullptr, albedo + q * 4, out + q * 4);
     if (VAR && var_out) memcpy(var_out, planes[p.iterations % 2].data(), pixels * sizeof(double));
     return IZPI_OK;
   } catch (const std::bad_alloc&) {

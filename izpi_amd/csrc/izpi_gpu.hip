@@ -103,13 +103,14 @@ struct CtxBuf {
   void** p;
   size_t* cap;
 };
-constexpr size_t RENDER_BUFS = 7, CTX_BUFS = 22;
+constexpr size_t RENDER_BUFS = 7, CTX_BUFS = 23;
 std::array<CtxBuf, CTX_BUFS> ctx_buffers(izpi_ctx* c) {
 #define IZPI_BUF(name) CtxBuf{(void**)&c->d_##name, &c->name##_cap}
   return {IZPI_BUF(samples), IZPI_BUF(recs), IZPI_BUF(pool), IZPI_BUF(ring), IZPI_BUF(running), IZPI_BUF(state),
           IZPI_BUF(spill), IZPI_BUF(out), IZPI_BUF(tiles), IZPI_BUF(utiles), IZPI_BUF(bg), IZPI_BUF(post),
           IZPI_BUF(share), IZPI_BUF(gather), IZPI_BUF(cpart), IZPI_BUF(finq), IZPI_BUF(denoise),
-          IZPI_BUF(moments), IZPI_BUF(noisepart), IZPI_BUF(adapt), IZPI_BUF(dnvar), IZPI_BUF(ckpt)};
+          IZPI_BUF(moments), IZPI_BUF(noisepart), IZPI_BUF(adapt), IZPI_BUF(dnvar), IZPI_BUF(ckpt),
+          IZPI_BUF(demod)};
 #undef IZPI_BUF
 }
 uint64_t buffer_bytes(izpi_ctx* ctx, size_t n) {

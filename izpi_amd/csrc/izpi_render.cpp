@@ -8,10 +8,11 @@
 //               [--device 0 | --gpus N] [--seed 12345]
 //               [--sampler colour|normal|wireframe|albedo|spectral] [--ink r,g,b]
 //               [--progressive STEP [--snapshots PREFIX]]
-//               [--denoise [N] [--denoise-sigma c,n,a]]
+//               [--denoise [N] [--denoise-sigma c,n,a] [--denoise-demodulate]]
 //               [--progressive STEP --noise-threshold T [--noise-tolerated F] [--noise-floor L]
 //                [--min-samples K] [--noise-out se.pfm] [--adaptive [--samples-out n.pfm]]
-//                [--denoise-variance [N] [--denoise-sigma c,n,a] [--variance-floor F] [--variance-out v.pfm]]]
+//                [--denoise-variance [N] [--denoise-sigma c,n,a] [--variance-floor F] [--variance-out v.pfm]
+//                 [--denoise-demodulate]]]
 //               [--progressive STEP [--stop-after K] [--checkpoint FILE] [--resume FILE]]
 //
 // --checkpoint FILE (with --progressive STEP) writes the session's checkpoint (DESIGN.md section
@@ -30,6 +31,13 @@
 // frame (the guides at 4 samples) are rendered to host memory and filtered on the device;
 // --out / --raw get the filtered canvas. --denoise-sigma sets sigma_colour, sigma_normal
 // and sigma_albedo (defaults 1, 0.5, 0.5).
+//
+// --denoise-demodulate (with --denoise on the Colour sampler, or with --denoise-variance) sets
+// IZPI_DENOISE_DEMODULATE: the filter runs on colour / albedo and the
+// albedo is multiplied back, which keeps texture detail. The guide frames are then rendered at
+// --samples instead of 4: the dividing albedo must come from at least the frame's samples.
+// The --denoise message and the IZPI_DENOISE_VAR line then say `demodulated`, and
+// --variance-out is the variance of the demodulated canvas.
 //
 // --progressive STEP renders the frame in steps of STEP samples per pixel (a progressive
 // session, izpi_gpu_progressive_*) and --snapshots PREFIX writes PREFIX_<done>.pfm after each
@@ -135,7 +143,7 @@ int main(int argc, char** argv) {
   bool denoise = false;
   izpi_denoise_params dparams = {IZPI_DENOISE_DEFAULT_ITERATIONS, 0, IZPI_DENOISE_DEFAULT_SIGMA_COLOUR,
                                  IZPI_DENOISE_DEFAULT_SIGMA_NORMAL, IZPI_DENOISE_DEFAULT_SIGMA_ALBEDO};
-  bool dvar = false, sigma_given = false;
+  bool dvar = false, sigma_given = false, demodulate = false;
   uint32_t dvar_iterations = IZPI_DENOISE_DEFAULT_ITERATIONS;
   double variance_floor = IZPI_DENOISE_VAR_DEFAULT_FLOOR;
   std::string variance_out;
@@ -186,6 +194,7 @@ int main(int argc, char** argv) {
       dvar = true;
       if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') dvar_iterations = (uint32_t)atoi(argv[++i]);
     }
+    else if (a == "--denoise-demodulate") demodulate = true;
     else if (a == "--variance-floor") variance_floor = atof(val().c_str());
     else if (a == "--variance-out") variance_out = val();
     else if (a == "--noise-threshold") { noise = true; nparams.threshold = atof(val().c_str()); }
@@ -215,6 +224,8 @@ int main(int argc, char** argv) {
   if (dvar && !noise) die("--denoise-variance needs --progressive and --noise-threshold");
   if (dvar && denoise) die("--denoise-variance and --denoise are two filters: name one");
   if (!variance_out.empty() && !dvar) die("--variance-out needs --denoise-variance");
+  if (demodulate && !denoise && !dvar) die("--denoise-demodulate needs --denoise or --denoise-variance");
+  if (demodulate) dparams.flags |= IZPI_DENOISE_DEMODULATE;
   if (dvar) {
     dparams.iterations = dvar_iterations;
     if (!sigma_given) dparams.sigma_colour = IZPI_DENOISE_VAR_DEFAULT_SIGMA_COLOUR;
@@ -263,6 +274,7 @@ int main(int argc, char** argv) {
   else sampler_name = sampler == IZPI_SAMPLER_SPECTRAL ? "spectral" : "colour";
   const bool spectral = sampler == IZPI_SAMPLER_SPECTRAL;
   if (denoise && sampler != IZPI_SAMPLER_COLOUR && !spectral) die("--denoise needs --sampler colour or spectral");
+  if (denoise && demodulate && spectral) die("--denoise-demodulate needs --sampler colour: a spectral frame has no albedo guide");
   if (denoise && progressive) die("--denoise filters a whole frame: not with --progressive");
   if (denoise && png) die("--denoise filters linear values: not with --png-pipeline");
   if (adaptive && sampler != IZPI_SAMPLER_COLOUR && !spectral) die("--adaptive needs --sampler colour or spectral");
@@ -328,7 +340,7 @@ int main(int argc, char** argv) {
     std::vector<izpi_render_stats> gst(stv.size());
     izpi_render_req g = req;
     g.post = IZPI_POST_NONE;
-    g.spp = 4;  // render_denoised's aov_spp
+    g.spp = demodulate ? spp : 4;  // render_denoised's aov_spp
     g.sampler = which;
     into.resize(canvas.size());
     if (multi ? izpi_gpu_multi_render(multi, &g, into.data(), gst.data()) : izpi_gpu_render(ctx, &g, into.data(), gst.data()))
@@ -438,8 +450,8 @@ int main(int argc, char** argv) {
                              plane.data(), W, H, &dparams, variance_floor, &ms))
       die(izpi_gpu_last_error(ctx));
     canvas.swap(filtered);
-    fprintf(stderr, "IZPI_DENOISE_VAR iterations=%u sigma_colour=%.6g floor=%.6g ms=%.3f\n", dparams.iterations,
-            dparams.sigma_colour, variance_floor, ms);
+    fprintf(stderr, "IZPI_DENOISE_VAR iterations=%u sigma_colour=%.6g floor=%.6g ms=%.3f%s\n", dparams.iterations,
+            dparams.sigma_colour, variance_floor, ms, demodulate ? " demodulated" : "");
     if (!variance_out.empty()) {
       std::vector<double> v4(canvas.size());
       for (size_t q = 0; q < plane.size(); q++) v4[4 * q] = v4[4 * q + 1] = v4[4 * q + 2] = plane[q];
@@ -456,7 +468,8 @@ int main(int argc, char** argv) {
                          &dparams, &ms))
       die(izpi_gpu_last_error(ctx));
     canvas.swap(filtered);
-    fprintf(stderr, "izpi-render: denoised, %u iterations, %.3f ms on the device\n", dparams.iterations, ms);
+    fprintf(stderr, "izpi-render: denoised%s, %u iterations, %.3f ms on the device\n", demodulate ? " (demodulated)" : "",
+            dparams.iterations, ms);
   }
   izpi_render_stats st = stv[0];
   for (size_t i = 1; i < stv.size(); i++) { st.rays += stv[i].rays; st.node_visits += stv[i].node_visits; }

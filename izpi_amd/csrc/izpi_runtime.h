@@ -205,6 +205,7 @@ struct izpi_ctx {
   double* d_gather = nullptr; size_t gather_cap = 0;  // multi-GPU root: every device's packed tiles
   double* d_denoise = nullptr; size_t denoise_cap = 0;  // the two denoisers' scratch canvas (denoise.hip; it only grows)
   double* d_dnvar = nullptr; size_t dnvar_cap = 0;  // izpi_gpu_denoise_var_device's two variance planes (denoise.hip; it only grows)
+  double* d_demod = nullptr; size_t demod_cap = 0;  // IZPI_DENOISE_DEMODULATE's demodulated canvas D_0 (denoise.hip; it only grows)
   // a session begun with IZPI_PROG_NOISE (noise.hip; both only grow, and no workspace plan counts them):
   double* d_moments = nullptr; size_t moments_cap = 0;  // the samples' second moments, [num_pixels][3]
   double* d_noisepart = nullptr; size_t noisepart_cap = 0;  // k_noise_stats' block partials: [blocks] sums, then [blocks][4] counts

@@ -417,7 +417,7 @@ class ProgressiveSession:
             raise ValueError("a multi-GPU session snapshots into host memory")
         self._call("snapshot_device", int(form), C.c_void_p(out_ptr))
 
-    def denoised(self, guides, params=None, variance_floor=None, post=N.POST_NONE):
+    def denoised(self, guides, params=None, variance_floor=None, post=N.POST_NONE, demodulate=False):
         """The frame after `done` >= 2 samples through the variance-guided filter (DESIGN.md
         3.8a), of a single-GPU noise session begun with post=N.POST_NONE over the whole canvas:
         the CANVAS and the NOISE snapshot into device canvases, izpi_gpu_denoise_var_device on
@@ -427,7 +427,13 @@ class ProgressiveSession:
         space, ahead of FireflyRejection), then N.POST_GAMMA_CLAMP's Gamma and Clamp. An
         adaptive session needs nothing more: its snapshots already divide by the pixels' own
         counts. Returns (canvas, variance): host arrays, the variance (H, W) that of the
-        filtered frame before `post`. The session's sums are not touched."""
+        filtered frame before `post`. The session's sums are not touched.
+        demodulate=True sets N.DENOISE_DEMODULATE on `params` (or on the defaults): the filter
+        runs on colour / albedo and the albedo is multiplied back; `guides`
+        must hold the Albedo frame, and the variance returned is the demodulated canvas's. The
+        dividing albedo wants at least the frame's samples: take the guides with
+        render_guides(aov_spp=the session's cap). A 4-sample albedo under a 64-sample frame
+        measured worse than no filter (the last row of 3.8b's table)."""
         r = self._owner
         if r._group:
             raise ValueError("a multi-GPU session gathers its snapshots; filter them on izpi_gpu_multi_context(m, 0)")
@@ -436,6 +442,11 @@ class ProgressiveSession:
         if post & N.POST_SPECTRAL and self._req.sampler != N.SAMPLER_SPECTRAL:
             raise ValueError("N.POST_SPECTRAL needs the Spectral sampler")
         normal, albedo = guides
+        if demodulate:
+            if albedo is None:
+                raise ValueError("demodulate=True needs guides with the Albedo frame")
+            params = N.denoise_var_params(demodulate=True) if params is None else N.DenoiseParams.from_buffer_copy(params)
+            params.flags |= N.DENOISE_DEMODULATE
         shape = (self._req.height, self._req.width, 4)
         colour, se, out, var = r._device_zeros(shape, shape, shape, shape[:2])
         self.snapshot_device(colour.data_ptr(), N.SNAP_CANVAS)
@@ -697,7 +708,10 @@ class GPURenderer(_Renderer):
         """The Normal frame and (albedo=True; the default for Colour, off for Spectral) the
         Albedo frame of this view at `aov_spp` samples, as device canvases (torch tensors):
         (normal, albedo or None), the guides of ProgressiveSession.denoised. Call it before the
-        session is opened: renders are refused while one is open."""
+        session is opened: renders are refused while one is open. Guides for
+        denoised(demodulate=True) want `aov_spp` at the session's cap: the albedo a frame is
+        divided by must come from at least the frame's samples (a 4-sample albedo under a
+        64-sample frame measured worse than no filter, the last row of DESIGN.md 3.8b's table)."""
         if albedo is None:
             albedo = self.sampler != N.SAMPLER_SPECTRAL
         guides = self._device_zeros(*[(self.height, self.width, 4)] * (2 if albedo else 1))
@@ -710,17 +724,29 @@ class GPURenderer(_Renderer):
             self.sampler, self.stats = own, stats  # (the frame's, not the guides')
         return guides[0], guides[1] if albedo else None
 
-    def render_denoised(self, spp=None, aov_spp=4, params=None, post=N.POST_NONE, albedo=None):
+    def render_denoised(self, spp=None, aov_spp=None, params=None, post=N.POST_NONE, albedo=None, demodulate=False):
         """A denoised frame of this renderer's sampler (Colour, or Spectral through
         POST_SPECTRAL) at `spp` samples (None: self.spp): the frame, then the Normal frame and
         (albedo=True; the default for Colour, off for Spectral, whose scenes may carry no RGB
         albedo) the Albedo frame at `aov_spp`, all into device canvases, then the filter on
         the linear values, then `post`'s Gamma / Clamp. Returns the host canvas;
         self.last_noisy keeps the unfiltered frame (before Gamma / Clamp) and
-        self.denoise_ms the filter's device time."""
+        self.denoise_ms the filter's device time. aov_spp None means 4, or with demodulate
+        the frame's `spp`. demodulate=True (Colour only) sets N.DENOISE_DEMODULATE on `params`
+        (or on the defaults): the filter runs on colour / albedo and the albedo is multiplied
+        back, which keeps texture detail."""
         if self.sampler not in (N.SAMPLER_COLOUR, N.SAMPLER_SPECTRAL):
             raise ValueError("render_denoised needs the Colour or the Spectral sampler")
         spectral = self.sampler == N.SAMPLER_SPECTRAL
+        if demodulate:
+            if spectral:
+                raise ValueError("demodulate=True needs the Colour sampler: a Spectral frame has no Albedo guide")
+            if albedo is not None and not albedo:
+                raise ValueError("demodulate=True needs the Albedo frame: not with albedo=False")
+            params = N.denoise_params(demodulate=True) if params is None else N.DenoiseParams.from_buffer_copy(params)
+            params.flags |= N.DENOISE_DEMODULATE
+        if aov_spp is None:
+            aov_spp = (self.spp if spp is None else spp) if demodulate else 4
         colour, out = self._device_zeros(*[(self.height, self.width, 4)] * 2)
         self.render_device(colour.data_ptr(), spp=spp, post=N.POST_SPECTRAL if spectral else N.POST_NONE)
         normal, albedo = self.render_guides(aov_spp, not spectral if albedo is None else albedo)
